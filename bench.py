@@ -9,6 +9,11 @@ with the raw xyz cloud already resident in HBM when the timed region starts.  On
 full pass over one cloud.  value = hypotheses scored by all ranks / max-over-ranks wall time.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg1|cfg3|cfg5] [--no-cpu]
+                    [--dump-outputs DIR]
+
+--steps K is the number of timed steps (default 10; 30 frames for cfg5) and ms_per_step the time of one.
+--dump-outputs DIR: after the timed steps, what the last one handed its caller is written to DIR as .npy
+files (see dump_outputs); the inputs depend on the arguments alone, so two builds can be compared.
 
 --config cfg5 (BASELINE.json configuration 5): a 30 Hz stream -- `steps` frames of ONE scene whose
 objects drift a few millimetres per frame, 2 000 samples per frame, through ag2_detect_frame (the
@@ -188,7 +193,7 @@ def validate_against_unsplit(capi, device, prm, weights, xyz_full, ordered, seed
     return out
 
 
-def stream_legs(seed, n_frames, n_warm, S=None, only=None, host_leg=True):
+def stream_legs(seed, n_frames, n_warm, S=None, only=None, host_leg=True, last=None):
     """BASELINE.json configuration 5: `n_frames` (+ n_warm untimed) RAW frames of one drifting tabletop scene
     (~765 000 points each, ~300 000 voxels of 3 mm) through ag2_detect_frame_raw -- workspace filter, voxel
     grid and uniform sub-sampling on the device inside the per-frame pipeline, which is captured in a
@@ -196,7 +201,8 @@ def stream_legs(seed, n_frames, n_warm, S=None, only=None, host_leg=True):
     (ag2_preprocess_cloud_device + ag2_subsample_uniformly + ag2_compute_normals + ag2_detect on a second
     context; must return the same bytes) and, for the front end's share, frames that arrive already
     preprocessed (ag2_detect_frame).  Latency = host time of one call: raw cloud in HBM -> selected grasps
-    in host memory."""
+    in host memory.  `last` (a dict), if given, receives the selection and scored count of the graph leg's
+    (with `only`: that leg's) last frame."""
     import torch
     from agile_grasp2_amd import capi, scene
     from agile_grasp2_amd.weights import make_lenet_weights
@@ -265,6 +271,8 @@ def stream_legs(seed, n_frames, n_warm, S=None, only=None, host_leg=True):
                                                     voxel_size=scene.VOXEL)
             dt = time.perf_counter() - t0
             out.append(sel.tobytes())
+            if last is not None and name == (only or "graph"):
+                last["sel"], last["n_scored"] = sel, n_sc
             if name == "stepwise" and not only:   # (kept on the host until the leg is over: a device allocation
                 pre[k] = (d.get_cloud()[0], d.get_samples())   #  between two frames can stall the next one)
             if k >= n_warm:
@@ -329,14 +337,22 @@ def stream_legs(seed, n_frames, n_warm, S=None, only=None, host_leg=True):
 
 def bench_stream(args):
     """--config cfg5: the frame stream as its own bench line (see stream_legs)."""
+    only = os.environ.get("AG2_STREAM_LEG")   # profiling aid: run one leg only
+    if only and only not in ("graph", "plain", "stepwise"):
+        # (graph_preprocessed replays the frames the stepwise leg preprocessed: it cannot run alone)
+        raise SystemExit(f"AG2_STREAM_LEG={only}: one of graph, plain, stepwise")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback for the measured path)")
     n_points, S, R, _, _ = CONFIGS["cfg5"]
     S = int(os.environ.get("AG2_STREAM_S", S))   # experiment aid: other sample counts on the same stream
     n_frames, n_warm = args.steps, max(3, args.warmup)   # warm-up: step-by-step, plain run + capture, first replay
-    only = os.environ.get("AG2_STREAM_LEG")   # profiling aid: run one leg only
-    lat = stream_legs(args.seed, n_frames, n_warm, S=S, only=only)
+    last = {}
+    lat = stream_legs(args.seed, n_frames, n_warm, S=S, only=only, last=last)
+    if args.dump_outputs:
+        if "sel" not in last:
+            raise SystemExit(f"--dump-outputs: the {only or 'graph'} leg returned no frame")
+        dump_outputs(args.dump_outputs, last["sel"], last["n_scored"])
     if only:
         print(json.dumps(lat), flush=True)
         return
@@ -425,10 +441,35 @@ def side_cfg3(args, weights, local_rank, steps=5):
                          "mean_P": c.sum_p / max(1, c.n_hypotheses), "list_points": int(c.list_points)}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, sel, n_scored):
+    """--dump-outputs: the result of the last timed step as its caller receives it -- the selected grasps
+    (one float64 array per field of the record; the integer fields are exact in float64; the padding field is
+    left out) and the number of hypotheses scored.  Should the records ever exceed DUMP_LIMIT_BYTES, a fixed,
+    seeded sample of them is written (its row numbers in selected_rows.npy)."""
+    fields = [f for f in sel.dtype.names if f != "reserved"]
+    row_bytes = sum(8 * int(np.prod(sel.dtype[f].shape or (1,))) for f in fields)
+    rows = np.arange(len(sel))
+    if len(sel) * row_bytes > DUMP_LIMIT_BYTES // 2:
+        keep = DUMP_LIMIT_BYTES // 2 // row_bytes
+        rows = np.sort(np.random.default_rng(0).choice(len(sel), size=keep, replace=False))
+    arrays = {"selected_" + f: np.ascontiguousarray(sel[f][rows], dtype=np.float64) for f in fields}
+    arrays["selected_rows"] = rows.astype(np.float64)
+    arrays["n_selected"] = np.array([len(sel)], dtype=np.float64)
+    arrays["n_scored"] = np.array([n_scored], dtype=np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 10; cfg5: 30 frames)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
@@ -438,10 +479,14 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="N > 1: weak = num_samples per GPU fixed (default, what the driver's scaling run uses), "
                          "strong = the configuration's num_samples in total, split over the GPUs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR as .npy files (float64)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 30 if args.config == "cfg5" else 10   # cfg5: SURVEY.md section 8d, 30 frames
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "cfg5":
-        if args.steps == 10:
-            args.steps = 30   # 30 frames
         return bench_stream(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -529,6 +574,7 @@ def main():
         size_exchange(xch["cap"])
 
     acc = {}
+    last = {}   # the selection the latest local step returned (a copy: detect() hands out its own array)
 
     def local_step(local_select=True):  # this rank's part of a step: no collective
         d.set_cloud_device(xyz_dev.data_ptr(), xyz.shape[0], 12)
@@ -536,6 +582,7 @@ def main():
         # (a rank of a multi-GPU run leaves the top-k to the merge: no local read-back)
         sel, n_scored = d.detect(sample_idx=idx, slot_base=slot_base, seed=args.seed, do_prune=True,
                                  want_all=False, local_select=local_select)
+        last["sel"] = sel
         return n_scored
 
     import ctypes
@@ -597,13 +644,16 @@ def main():
         t0 = time.perf_counter()
         scored = 0
         for _ in range(args.steps):
-            scored += step()
+            n_last = step()
+            scored += n_last
             read_times(d.h, t_ref)
             acc_sweep[0] += t.sweep_ms
             acc_sweep[1] += t.sweep_overflow_ms
         sync()
         elapsed = time.perf_counter() - t0
     acc["sweep_ms"], acc["sweep_overflow_ms"] = acc_sweep
+    # what the last timed step returned (N > 1: the merged selection every rank holds); later passes reuse d
+    last_sel = xch["merged"] if dist_on else last["sel"]
     c = d.counters()
 
     if dist_on:  # no rank's list may have been cut (the headers say): else the bench line is void
@@ -612,7 +662,7 @@ def main():
             raise SystemExit(f"exchange capacity {xch['cap']} too small: {hdr[:, 0].tolist()}")
     sweep_rank_ms = (acc.get("sweep_ms", 0.0) + acc.get("sweep_overflow_ms", 0.0)) / max(1, args.steps)
     tt = torch.tensor([elapsed, float(scored), float(c.n_hypotheses), float(xyz.shape[0]), float(s_rank),
-                       sweep_rank_ms], dtype=torch.float64, device=coll_dev)
+                       sweep_rank_ms, float(n_last)], dtype=torch.float64, device=coll_dev)
     per_rank = None
     if dist_on:
         tmax = tt.clone()
@@ -629,9 +679,12 @@ def main():
                     "steps_repeated_rank0": int(xch.get("retries", 0)),
                     "rank0_detect_one_trip": int(c.detect_one_trip), "rank0_detect_redone": int(c.detect_redone)}
     total_scored = float(tt[1])
+    last_scored = float(tt[6])   # the last timed step's count, all ranks (N > 1: summed like total_scored)
     if rank != 0:
         dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_sel, last_scored)
     if dist_on:
         per_rank["matches_unsplit"] = validate_against_unsplit(capi, local_rank, prm, weights, xyz_full, ordered, args.seed,
                                                               xch["merged"], int(xch["n_total"]), total_scored / args.steps)

@@ -4,7 +4,7 @@
  *
  * TEST INFRASTRUCTURE ONLY (see ag2_oracle.h).  PARITY UNPINNED against the real reference: it has
  * no tests/fixtures and cannot be built here; third-party numerics (PCL, Eigen, OpenCV, Caffe) are
- * restated from their documented behaviour.  All paths cited below are relative to /root/reference.
+ * restated from their documented behaviour.  All paths cited below are relative to the reference tree (gwding/agile_grasp2).
  *
  * Arithmetic contract (shared with the HIP kernels, which must reproduce it bit for bit):
  *   - only IEEE-754 +,-,*,/,sqrt,floor and comparisons on the parity-critical path; every

@@ -2,7 +2,7 @@
 
 Each function recomputes one stage of the reference algorithm a second way (brute force, LAPACK
 eigh, scipy.ndimage, torch-CPU conv) so that a mistake in oracle/ag2_oracle.cpp does not silently
-become the definition of "correct".  Citations are to /root/reference files.
+become the definition of "correct".  Citations are to files of the reference tree (gwding/agile_grasp2).
 """
 from __future__ import annotations
 

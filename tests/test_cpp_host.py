@@ -372,10 +372,28 @@ def test_cpp_frames_of_the_raw_cloud_equal_the_two_calls(tmp_path, min_inliers):
     assert runs[0] == runs[1] == runs[2] == runs[3]
 
 
+def launch_file_text():
+    """A launch file with the reference's parameters (tests/golden/reference_constants.json) in the layout
+    of its file_detect_grasps.launch: decoy values for num_samples and workspace inside comments."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_constants.json")) as f:
+        ref = json.load(f)
+    lines = ['<launch>', '\t<node name="detect_grasps_file" pkg="agile_grasp2" type="detect_grasps_file" output="screen">',
+             '<!--', '    <param name="num_samples" value="1" /> ', '-->',
+             '<!-- <rosparam param="workspace"> [0, 1, 0, 1, 0, 1] </rosparam> --> <!-- other scene -->']
+    lines += [f'    <rosparam param="{k}"> {v} </rosparam>' for k, v in ref["launch_rosparams"]]
+    for i, (k, v) in enumerate(ref["launch_params"]):
+        tail = ' <!-- 0: "a", 1: b -->' if i % 3 == 0 else ("    " if i % 3 == 1 else "")
+        lines.append(f'    <param name="{k}" value="{v}"{"/>" if i % 2 else " />"}{tail}')
+    lines += ['\t</node>', '</launch>', '']
+    return "\n".join(lines)
+
+
 def test_launch_xml_and_keyvalue_readers(tmp_path):
-    """Params readers accept the reference's own launch file text (parameter NAMES are the
-    contract; the file is read at test time from /root/reference when present, else a literal
-    excerpt of its parameter names is used)."""
+    """Params readers accept the reference's own launch file (parameter NAMES are the contract): a
+    literal excerpt of its parameter names, and a file laid out like the reference's own (comments that
+    hide parameters, trailing comments, tabs, unused parameters) holding every parameter it sets, in its
+    order, with its values (tests/golden/reference_constants.json)."""
     src = r'''
 #include <cstdio>
 #include <fstream>
@@ -419,13 +437,11 @@ int main(int argc, char** argv) {
     <param name="min_score_diff" value="300" /> <param name="batch_size" value="100" />
     <param name="min_inliers" value="5" /> <param name="num_selected" value="30" />
     </node></launch>'''
-    ref_launch = "/root/reference/launch/file_detect_grasps.launch"
-    if os.path.exists(ref_launch):
-        xml = open(ref_launch).read()  # read as data at test time; nothing is copied into the repo
-    lx = os.path.join(tmp, "l.launch")
-    open(lx, "w").write(xml)
-    out = subprocess.check_output([exe, lx, "xml"], text=True).split()
-    assert out == ["5000", "8", "0.01", "300", "30", "0.92", "6", "0.08", "0", "5", "0.1"], out
+    for k, text in enumerate((xml, launch_file_text())):
+        lx = os.path.join(tmp, f"l{k}.launch")
+        open(lx, "w").write(text)
+        out = subprocess.check_output([exe, lx, "xml"], text=True).split()
+        assert out == ["5000", "8", "0.01", "300", "30", "0.92", "6", "0.08", "0", "5", "0.1"], (k, out)
     kv = os.path.join(tmp, "k.txt")
     open(kv, "w").write("num_samples=77 # comment\ninit_bite = 0.02\nworkspace=[1,2,3,4,5,6]\n")
     out = subprocess.check_output([exe, kv, "kv"], text=True).split()

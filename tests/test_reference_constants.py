@@ -10,19 +10,18 @@ C-ABI library and the C++ host mirror (no GPU needed: everything here is host-si
   * LeNet layer shapes: caffe/test_1batch2.prototxt:1-92
   * HandSearch's 7-argument constructor: include/agile_grasp2/hand_search.h:114-118
 
-The literals below are data copied out of those lines (a fixture).  When /root/reference is present
-(this container; never the GPU box) the test also re-reads the reference's files as text and checks
-that the fixture still says what they say.
+The literals below are data copied out of those lines (a fixture).  tests/golden/reference_constants.json
+holds the same values as tests/golden/make_reference_constants.py reads them out of the reference's files;
+the first test checks that the literals still say what those files say.
 """
+import json
 import os
-import re
 import subprocess
 
 import numpy as np
-import pytest
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF_CONSTANTS = os.path.join(ROOT, "tests", "golden", "reference_constants.json")
 
 BASE_TF = np.array([[0, 0.445417, 0.895323, 0.215], [1, 0, 0, -0.015], [0, 0.895323, -0.445417, 0.23], [0, 0, 0, 1.0]])
 SQRT_TF = np.array([[0.9366, -0.0162, 0.3500, -0.2863], [0.0151, 0.9999, 0.0058, 0.0058],
@@ -48,30 +47,22 @@ def expected_finger_spacing(od, fw, n=N_SLOTS_PER_SIDE):
     return np.concatenate([half - od + fw, half])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only in the build container")
 def test_fixture_literals_are_what_the_reference_files_say():
-    txt = open(os.path.join(REF, "src/agile_grasp2/grasp_detector.cpp")).read()
+    with open(REF_CONSTANTS) as f:
+        ref = json.load(f)
     for name, want in (("base_tf", BASE_TF), ("sqrt_tf", SQRT_TF)):
-        m = re.search(name + r"\s*<<([^;]*);", txt)
-        got = np.array([float(v) for v in m.group(1).replace("\n", " ").split(",")]).reshape(4, 4)
+        got = np.array(ref[name]).reshape(4, 4)
         assert np.array_equal(got, want), name
-    fh = open(os.path.join(REF, "src/agile_grasp2/finger_hand.cpp")).read()
-    assert re.search(r"int n = 10;", fh) and "setLinSpaced(n, 0.0, hand_outer_diameter - finger_width)" in fh
-    assert "(fs_half.array() - hand_outer_diameter_ + finger_width_).matrix(), fs_half" in fh
-    proto = open(os.path.join(REF, "caffe/test_1batch2.prototxt")).read()
-    assert tuple(int(v) for v in re.findall(r"dim:\s*(\d+)", proto)) == LENET_INPUT
-    layers = re.findall(r'layer\s*\{\s*name:\s*"(\w+)"\s*type:\s*"(\w+)"(.*?)(?=layer\s*\{|\Z)', proto, flags=re.S)
-    assert [(n, t) for n, t, _ in layers] == [(n, t) for n, t, _ in LENET_LAYERS]
-    for (n, t, body), (_, _, want) in zip(layers, LENET_LAYERS):
+    assert ref["finger_slots_per_side"] == N_SLOTS_PER_SIDE
+    assert tuple(ref["lenet_input"]) == LENET_INPUT
+    assert [(n, t) for n, t, _ in ref["lenet_layers"]] == [(n, t) for n, t, _ in LENET_LAYERS]
+    for (n, t, got), (_, _, want) in zip(ref["lenet_layers"], LENET_LAYERS):
         for key, val in want.items():
-            m = re.search(key + r":\s*(\w+)", body)
-            assert m and m.group(1) == str(val), (n, key)
-    hs = open(os.path.join(REF, "include/agile_grasp2/hand_search.h")).read()
-    assert "nn_radius_taubin_(0.03)" in hs and "nn_radius_hands_(0.08)" in hs
-    launch = open(os.path.join(REF, "launch/file_detect_grasps.launch")).read()
+            assert key in got and str(got[key]) == str(val), (n, key)
+    assert ref["hand_search_default_nn_radius_taubin"] == 0.03 and ref["hand_search_default_nn_radius_hands"] == 0.08
+    launch = dict(ref["launch_params"])
     for key, val in LAUNCH_HAND.items():
-        m = re.search(r'name="%s"\s+value="([^"]+)"' % key, launch)
-        assert m and float(m.group(1)) == float(val), key
+        assert key in launch and float(launch[key]) == float(val), key
 
 
 def test_finger_slots_angles_depths_oracle_and_library():
