@@ -279,7 +279,6 @@ struct ag2_ctx {
   // hipFuncSetAttribute is per device: which of the large-dynamic-LDS kernels this context has prepared on ITS
   // device (bits kAttr*); a process-wide flag left devices >= 1 without the attribute
   unsigned func_attr_done = 0;
-  ag2::DevBuf d_sweep_prof;  // diagnostic only (AG2_SWEEP_PROF): per-phase cycle sums of the sweep kernels
   // how the host waits for a kernel's flag in page-locked memory (ag2_set_wait_mode): 0 the stream
   // (hipStreamSynchronize), 1 poll; spin_us: busy polling before the poller starts yielding its core
   int wait_poll = 1;

@@ -7,10 +7,6 @@
 #include "ag2_internal.h"
 #include "k_grid_common.h"
 
-#ifndef AG2_SCAN_PER
-#define AG2_SCAN_PER 8
-#endif
-
 namespace ag2 {
 
 __global__ void k_init_stats(DevStats* st) {
@@ -179,7 +175,7 @@ __global__ void __launch_bounds__(256) k_cell_count(const float4* __restrict__ x
 // POPC: the input is the population count of src[i] (i < n - 1; element n - 1 counts as zero, so
 // data[n - 1] receives the total) -- the voxel front end's rank-per-bitmap-word scan, without a pass that
 // writes the counts first.
-constexpr int kScanPer = AG2_SCAN_PER;          // elements per thread
+constexpr int kScanPer = 8;                     // elements per thread
 constexpr int kScanTile = 256 * kScanPer;       // ... per tile
 template <bool POPC>
 __global__ void __launch_bounds__(256) k_scan_chained(unsigned* __restrict__ data, int n,

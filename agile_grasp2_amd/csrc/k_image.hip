@@ -153,15 +153,14 @@ __device__ __forceinline__ double block_min_y(const double* __restrict__ pts, in
 
 // The images of one renderer as a dense list, handed out through a counter: a renderer's images differ by a
 // factor of four in their point counts, and a static deal of a few of them to every workgroup ends with most
-// of the GPU waiting for the unluckiest one.  list == nullptr: all images in turn, each kernel skipping the
-// others' by the point count (when only one renderer runs there is nothing to balance).
+// of the GPU waiting for the unluckiest one.  The queued renderers keep the other renderers' (n_img, d_n)
+// arguments unused: the queue's count is their list length.
 struct ImgQueue {
   const int* list;        // image indices of this renderer
   const unsigned* count;  // how many
   unsigned* next;         // zero at launch; a workgroup takes gridDim.x + (this++) when it is done with an image
 };
 __device__ __forceinline__ int img_queue_next(const ImgQueue& q, int w, int* s_next, int& it) {
-  if (!q.list) return w + (int)gridDim.x;
   if (threadIdx.x == 0) s_next[it & 1] = (int)gridDim.x + (int)atomicAdd(q.next, 1u);
   __syncthreads();
   const int v = __builtin_amdgcn_readfirstlane(s_next[it & 1]);
@@ -402,14 +401,13 @@ __global__ void __launch_bounds__(kImgThreads, 4) k_render_sparse(const double* 
   }
 }
 
-// k_render_sorted (kSortedMax < P <= kSortedMaxBig, dense clouds; AG2_RENDER_BITONIC=1: also the range of
-// k_render_counted below, for A/B): the points' (cell, list position)
+// k_render_sorted (kSortedMax < P <= kSortedMaxBig, dense clouds): the points' (cell, list position)
 // keys are sorted in LDS (bitonic, the position in the low bits keeps list order inside a cell), so
 // every cell's points sit together; the thread that finds the head of a run adds the run's normals
 // in list order -- the same f64 sums as the reference's scan over all points for each cell, at
 // O(P log^2 P) instead of O(3600 P).
-// Two instantiations: up to 16384 points (96 KB of LDS, one workgroup per CU) and up to 4096 (48 KB, three per
-// CU: the A/B twin of k_render_counted); NBITS = bits of the list position inside a key.
+// Instantiated for up to 16384 points (96 KB of LDS, one workgroup per CU); NBITS = bits of the list position
+// inside a key.
 constexpr int kSortedMax = 4096, kSortedMaxBig = 16384;
 constexpr int kWalk = 768;         // sorted positions whose normals are staged in LDS at a time
 template <int NMAX, int NT>
@@ -422,7 +420,6 @@ struct SortedShared {
 };
 static_assert(kWalk * 3 * 8 >= kCells * 3, "output staging must fit the normal stage");
 static_assert(kCells <= 4096, "12 bits for the cell");
-static_assert(sizeof(SortedShared<kSortedMax, kImgThreads>) * 3 <= 160 * 1024, "k_render_sorted: three workgroups per CU");
 static_assert(sizeof(SortedShared<kSortedMaxBig, 1024>) <= 160 * 1024, "k_render_sorted, big: one workgroup per CU");
 
 // Bitonic sort (ascending) of PER * NT keys held PER per thread: element index = tid * PER + r.
@@ -495,19 +492,18 @@ __global__ void __launch_bounds__(NT) k_render_sorted(const double* __restrict__
                                                                int n_img, const unsigned* __restrict__ d_n,
                                                                int p_min, unsigned char* __restrict__ out, ImgQueue q) {
   static_assert((1 << NBITS) >= NMAX && NBITS + 12 < 32, "key layout");
-  if (d_n) n_img = min(n_img, (int)*d_n);  // frame mode: the list length is read on the device
   __shared__ int s_qnext[2];
   int qit = 0;
-  const int n_work = q.list ? (int)*q.count : n_img;
+  const int n_work = (int)*q.count;
   constexpr unsigned kPosMask = (1u << NBITS) - 1u;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_sorted[];
   SortedShared<NMAX, NT>& S = *reinterpret_cast<SortedShared<NMAX, NT>*>(smem_sorted);
   const int tid = threadIdx.x;
   for (int w = blockIdx.x; w < n_work; w = img_queue_next(q, w, s_qnext, qit)) {
-    const int im = q.list ? q.list[w] : w;
+    const int im = q.list[w];
     const long long off = desc_off[im];
     const int P = (off >= 0) ? desc_cnt[im] : 0;
-    if (P < p_min || P > NMAX) continue;  // the other renderers' images (uniform)
+    if (P < p_min || P > NMAX) continue;  // (uniform; k_render_classify lists only this range: a bound of S)
     const double* pts = arena + (size_t)off * 6;
     __syncthreads();  // previous image's readers of S are done
     // x and y of this thread's points are read ONCE, all loads in flight together (the kernel is
@@ -657,19 +653,18 @@ __global__ void __launch_bounds__(kImgThreads, 3) k_render_counted(const double*
                                                                 const int* __restrict__ desc_cnt, int n_img,
                                                                 const unsigned* __restrict__ d_n, int p_min,
                                                                 unsigned char* __restrict__ out, ImgQueue q) {
-  if (d_n) n_img = min(n_img, (int)*d_n);  // frame mode: the list length is read on the device
   __shared__ CountedShared S;
   __shared__ int s_qnext[2];
   int qit = 0;
-  const int n_work = q.list ? (int)*q.count : n_img;
+  const int n_work = (int)*q.count;
   constexpr int NT = kImgThreads, NW = kCWaves, kChunks = 16;
   const int tid = threadIdx.x, lane = lane_id(), wid = wave_id();
   const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   for (int w = blockIdx.x; w < n_work; w = img_queue_next(q, w, s_qnext, qit)) {
-    const int im = q.list ? q.list[w] : w;
+    const int im = q.list[w];
     const long long off = desc_off[im];
     const int P = (off >= 0) ? desc_cnt[im] : 0;
-    if (P < p_min || P > kSortedMax) continue;  // the other renderers' images (uniform)
+    if (P < p_min || P > kSortedMax) continue;  // (uniform; k_render_classify lists only this range: a bound of S)
     const double* pts = arena + (size_t)off * 6;
     __syncthreads();  // previous image's readers of S are done
     // this wave's quarter of the list: seg positions (a multiple of 64) from wid * seg on
@@ -859,10 +854,8 @@ int launch_render(ag2_ctx* c, const double* d_arena, const long long* d_off, con
   hipLaunchKernelGGL(k_render_sparse, dim3((int)std::min<size_t>(n_img, 256 * 6)), dim3(kImgThreads), 0,
                      c->stream, d_arena, d_off, d_cnt, (int)n_img, d_n, d_out);
   // ... the rest: one list per renderer, handed out image by image (ImgQueue)
-  static const bool bitonic = getenv("AG2_RENDER_BITONIC") != nullptr;  // (A/B: the sorting-network renderer)
-  static const bool no_queue = getenv("AG2_RENDER_STATIC") != nullptr;  // (A/B: images dealt statically)
-  ImgQueue q[3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-  if (max_p > kSparseMax && !no_queue) {
+  ImgQueue q[3] = {};
+  if (max_p > kSparseMax) {
     AG2_HIP(c, c->d_rlist.reserve(32 + 3 * n_img * 4));
     unsigned* ctr = c->d_rlist.as<unsigned>();
     int* lists = reinterpret_cast<int*>(ctr + 8);
@@ -870,14 +863,9 @@ int launch_render(ag2_ctx* c, const double* d_arena, const long long* d_off, con
     hipLaunchKernelGGL(k_render_classify, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, c->stream, d_off, d_cnt,
                        (int)n_img, d_n, (int)n_img, ctr, lists);
     for (int k = 0; k < 3; k++) q[k] = ImgQueue{lists + (size_t)k * n_img, ctr + k, ctr + 4 + k};
-  }
-  if (max_p > kSparseMax && !bitonic)
     hipLaunchKernelGGL(k_render_counted, dim3((int)std::min<size_t>(n_img, 256 * 3)), dim3(kImgThreads), 0, c->stream,
                        d_arena, d_off, d_cnt, (int)n_img, d_n, kSparseMax + 1, d_out, q[0]);
-  if (max_p > kSparseMax && bitonic)
-    hipLaunchKernelGGL((k_render_sorted<kSortedMax, 12, kImgThreads>), dim3((int)std::min<size_t>(n_img, 256 * 3)),
-                       dim3(kImgThreads), sizeof(SortedShared<kSortedMax, kImgThreads>), c->stream, d_arena, d_off, d_cnt,
-                       (int)n_img, d_n, kSparseMax + 1, d_out, q[0]);
+  }
   if (max_p > kSortedMax)
     hipLaunchKernelGGL((k_render_sorted<kSortedMaxBig, 14, 1024>), dim3((int)std::min<size_t>(n_img, 256)),
                        dim3(1024), sizeof(SortedShared<kSortedMaxBig, 1024>), c->stream, d_arena, d_off,

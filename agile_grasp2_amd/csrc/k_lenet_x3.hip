@@ -34,17 +34,11 @@
 
 namespace ag2 {
 
-// ablation switches for tools/ab_build.sh (timing only, wrong results): 1 no conv1, 2 no conv2, 4 / 8 no A / B requests in conv2
-// Wave priority during conv1 of the banded kernel (s_setprio; 0 = leave it alone, for A/B).  The two workgroups of a
+// Wave priority during conv1 of the banded kernel (s_setprio).  The two workgroups of a
 // CU share every SIMD; conv2 of one saturates the matrix pipe by itself (round 4: conv2 alone is as fast with one
 // workgroup per CU as with two), so the other's conv1 -- few MFMAs, much vector work -- is the phase that should
 // win the arbitration: 0.1915 -> 0.188 ms at 934 images (same bits: scheduling only).
-#ifndef AG2_CONV1_PRIO
-#define AG2_CONV1_PRIO 2
-#endif
-#ifndef AG2_EXP_ABL
-#define AG2_EXP_ABL 0
-#endif
+constexpr int kConv1Prio = 2;
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -191,10 +185,7 @@ __device__ __forceinline__ void x3_conv2(const SH& S, const uint4* __restrict__ 
   auto step = [&](int b, auto K_, auto TC_, auto TN_) {
     constexpr int K = decltype(K_)::value;
     constexpr bool TC = decltype(TC_)::value, TN = decltype(TN_)::value;
-#if !(AG2_EXP_ABL & 8)
     load_b(min(b + 3, kLast), B[(K + 3) & 3]);  // (the last requests are repeats nobody uses)
-#endif
-#if !(AG2_EXP_ABL & 4)
     if constexpr (kAhead) {
       if constexpr (TN) load_a_tail(min(b + 1, kLast), A[(K + 1) & 1]);
       else load_a_main(b + 1, A[(K + 1) & 1]);
@@ -202,7 +193,6 @@ __device__ __forceinline__ void x3_conv2(const SH& S, const uint4* __restrict__ 
       if constexpr (TC) load_a_tail(b, A[0]);
       else load_a_main(b, A[0]);
     }
-#endif
     if constexpr (!kAhead) x3_fence();
     mma(A[kAhead ? (K & 1) : 0], B[K & 3]);
     if constexpr (kAhead) {
@@ -436,7 +426,7 @@ k_lenet_conv_x3(const unsigned char* __restrict__ images, int n_img, const unsig
 // reads, conversions and the packing.  Every output is the same chain of MFMAs in
 // the same k order as in the whole-image kernel: bit-identical results.  Measured (934 images): whole
 // image 0.276 ms, bands 0.245 ms at the time; 0.194 ms with the operand requests in the shadow of the
-// MFMAs (x3_conv2 / x3_conv1) -- ablations of the current kernel (AG2_EXP_ABL): conv2 alone 0.132 ms
+// MFMAs (x3_conv2 / x3_conv1) -- timing-only ablations of the kernel (round 4): conv2 alone 0.132 ms
 // (0.114 with no operand requests at all = the matrix pipe at the ~1.9 GHz this kernel sustains), conv1
 // alone 0.058 ms (pipe: 0.029), neither 0.008 ms.
 constexpr int kBThreads = 256;
@@ -502,17 +492,13 @@ k_lenet_conv_x3b(const unsigned char* __restrict__ images, int n_img, const unsi
       uint4 W[kXC1Blocks][3];
       x3_conv1_weights(w1x, ln, W);
       if (u + (int)gridDim.x < units) fetch(u + gridDim.x);  // (after the weights: waiting for those does not wait for these)
-#if !(AG2_EXP_ABL & 1)
-#if AG2_CONV1_PRIO
-      __builtin_amdgcn_s_setprio(AG2_CONV1_PRIO);
-#endif
+      __builtin_amdgcn_s_setprio(kConv1Prio);
       x3_conv1<X3Band, 4, kBWaves>(S, W, bias1, wid, ln, S.imgb);
       x3_conv1<X3Band, 4, kBWaves>(S, W, bias1, wid + 16, ln, S.imgb);
       // (tiles wid + 32, + 36 and, for waves 0 and 1, + 40: three tiles at once rather than a single
       // one with its chain of dependent MFMAs)
       if (wid < 2) x3_conv1<X3Band, 3, kBWaves>(S, W, bias1, wid + 32, ln, S.imgb);
       else x3_conv1<X3Band, 2, kBWaves>(S, W, bias1, wid + 32, ln, S.imgb);
-#endif
     }
     __syncthreads();
     // conv2: 6 tiles x 2 channel halves over 4 waves; the band's 48 windows follow the 48 band
@@ -520,12 +506,8 @@ k_lenet_conv_x3b(const unsigned char* __restrict__ images, int n_img, const unsi
     {
       int ln = lane;
       asm volatile("" : "+v"(ln));
-#if AG2_CONV1_PRIO
       __builtin_amdgcn_s_setprio(0);
-#endif
-#if !(AG2_EXP_ABL & 2)
       x3_conv2<X3Band, 3, 2>(S, w2x, pooled2 + (size_t)im * 7200 + band * (48 * 50), bias2, nh, mgrp, ln);
-#endif
     }
   }
 }
@@ -586,12 +568,6 @@ int lenet_pack_weights_x3(ag2_ctx* c, const float* c1w, const float* c2w) {
 // c + 2 -- the conversion, the LDS writes and every request are issued in the shadow of the MFMAs,
 // and a chunk costs one barrier.  (Staging, then MFMAs, two barriers per chunk: matrix pipes 49 %
 // busy.)
-// (AG2_EXP_FCABL: timing-only ablations of k_lenet_fc1_x3 -- wrong results -- for tools/ab_build.sh: 1 half of the
-//  A-fragment LDS reads, 2 no B-fragment loads in the loop, 4 no conversion / LDS writes, 8 no activation
-//  loads in the loop, 16 no MFMAs)
-#ifndef AG2_EXP_FCABL
-#define AG2_EXP_FCABL 0
-#endif
 constexpr int kFxBM = 128;
 constexpr int kFxKC = 32;              // k per chunk: 7200 = 225 chunks of two 16-k blocks
 constexpr int kFxPitch = 40;           // bf16 per staged row
@@ -663,9 +639,6 @@ k_lenet_fc1_x3(const float* __restrict__ x, int n_img, const unsigned* __restric
   const int nkb = chunks_per_split * 2;
   uint4 B[4][3];
   auto load_b = [&](int kb, uint4(&d)[3]) {
-#if AG2_EXP_FCABL & 2
-    if (kb > 1) return;
-#endif
     const uint4* wn = wl + (size_t)min(kb, nkb - 1) * (16 * 3 * 64);
     d[0] = wn[0];
     d[1] = wn[64];
@@ -674,20 +647,13 @@ k_lenet_fc1_x3(const float* __restrict__ x, int n_img, const unsigned* __restric
   // A fragments of two image tiles (t0, t0 + 1) for k-block kb of the chunk in buffer buf
   auto load_a = [&](int buf, int kbl, int t0, uint4(&d)[2][3]) {
 #pragma unroll
-    for (int t = 0; t < ((AG2_EXP_FCABL & 1) ? 1 : 2); t++)
+    for (int t = 0; t < 2; t++)
 #pragma unroll
       for (int s = 0; s < 3; s++)
         d[t][s] = *reinterpret_cast<const uint4*>(&S.a[buf][s][32 * (t0 + t) + r][16 * kbl + 8 * h]);
-#if AG2_EXP_FCABL & 1
-    for (int s = 0; s < 3; s++) d[1][s] = d[0][s];
-#endif
   };
   auto mma2 = [&](int t0, const uint4(&a)[2][3], const uint4(&bb)[3]) {
     constexpr int ia[6] = {0, 2, 1, 0, 1, 0}, ib[6] = {2, 0, 1, 1, 0, 0};  // hl, lh, mm, hm, mh, hh
-#if AG2_EXP_FCABL & 16
-    acc[t0][0] += __uint_as_float(a[0][0].x ^ a[1][1].y ^ a[0][2].z ^ a[1][0].w ^ bb[0].x ^ bb[1].y ^ bb[2].z);
-    return;
-#endif
 #pragma unroll
     for (int k = 0; k < 6; k++)
 #pragma unroll
@@ -718,9 +684,7 @@ k_lenet_fc1_x3(const float* __restrict__ x, int n_img, const unsigned* __restric
       if (hs == 2) load_b(2 * ci + 3, B[(2 * PAR + 3) & 3]);
       // next half-step's A fragments (the first of the next chunk come after the barrier)
       if (hs < 3) load_a(buf, (hs + 1) >> 1, 2 * ((hs + 1) & 1), A[(hs + 1) & 1]);
-#if !(AG2_EXP_FCABL & 4)
       lstore4(nbuf, hs, R[hs]);
-#endif
       mma2(t0, A[hs & 1], B[(2 * PAR + kbl) & 3]);
 #pragma unroll
       for (int i = 0; i < 12; i++) {
@@ -732,9 +696,7 @@ k_lenet_fc1_x3(const float* __restrict__ x, int n_img, const unsigned* __restric
       }
       x3_fence();
     }
-#if !(AG2_EXP_FCABL & 8)
     gload(ci + 3, R);  // (in flight for a chunk and a half)
-#endif
     __syncthreads();   // chunk ci + 1 is staged; every reader of this chunk's buffer is done
     load_a(nbuf, 0, 0, A[0]);
   };
@@ -813,9 +775,7 @@ int launch_lenet_conv_x3(ag2_ctx* c, const uint8_t* d_images, size_t n, float* d
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(X3Band)));
       c->func_attr_done |= kAttrLenetX3b;
     }
-    // (AG2_EXP_CONV_GRID: experiment -- another number of workgroups, e.g. 256 = one per CU)
-    static const int exp_grid = [] { const char* e = getenv("AG2_EXP_CONV_GRID"); return e ? atoi(e) : 0; }();
-    const int gridb = (int)std::min<size_t>(3 * n, exp_grid > 0 ? (size_t)exp_grid : 512);
+    const int gridb = (int)std::min<size_t>(3 * n, 512);
     hipLaunchKernelGGL(k_lenet_conv_x3b, dim3(gridb), dim3(kBThreads), sizeof(X3Band), c->stream, d_images,
                        (int)n, d_n, d.w1x.as<uint4>(), d.b1.as<float>(), d.w2x.as<uint4>(), d.b2.as<float>(),
                        d_pooled2);

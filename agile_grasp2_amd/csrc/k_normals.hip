@@ -11,11 +11,6 @@
 // algorithmic bytes = N * (K1 * 12 + 12).
 #include "ag2_internal.h"
 
-// ablation switches for tools/ab_build.sh (timing only, wrong results): 1 no Jacobi, 2 one stencil row
-// only, 4 no statistics atomic
-#ifndef AG2_EXP_NABL
-#define AG2_EXP_NABL 0
-#endif
 namespace ag2 {
 
 __global__ void __launch_bounds__(256) k_normals(const float4* __restrict__ pts,
@@ -127,9 +122,6 @@ __global__ void __launch_bounds__(256) k_normals(const float4* __restrict__ pts,
       nested_walk();
       nr = 0;
     }
-#if AG2_EXP_NABL & 2
-    nr = min(nr, 1);
-#endif
     // One flat walk over the spans, four points per step, with the NEXT step's four loads in flight
     // while this step's points are tested and accumulated: a thread's chain of dependent load round
     // trips overlaps its arithmetic instead of adding to it.  A step that reaches past its span reads
@@ -217,11 +209,7 @@ __global__ void __launch_bounds__(256) k_normals(const float4* __restrict__ pts,
       m.a11 = (double)(a3 - a7 * a7);
       m.a12 = (double)(a4 - a7 * a8);
       m.a22 = (double)(a5 - a8 * a8);
-#if AG2_EXP_NABL & 1
-      Eig3 e; e.d[0]=m.a00; e.d[1]=m.a11; e.d[2]=m.a22; e.v[0][0]=m.a01; e.v[0][1]=m.a02; e.v[0][2]=m.a12; e.v[1][0]=1; e.v[1][1]=0; e.v[1][2]=0; e.v[2][0]=0; e.v[2][1]=1; e.v[2][2]=0;
-#else
       const Eig3 e = jacobi3(m);
-#endif
       const int mi = argmin3(e.d);
       const V3 v{mi == 0 ? e.v[0][0] : (mi == 1 ? e.v[0][1] : e.v[0][2]),
                  mi == 0 ? e.v[1][0] : (mi == 1 ? e.v[1][1] : e.v[1][2]),
@@ -242,12 +230,10 @@ __global__ void __launch_bounds__(256) k_normals(const float4* __restrict__ pts,
   const int tot = wave_sum_i(cnt);
   if (lane_id() == 0) s_tot[wave_id()] = tot;
   __syncthreads();
-#if !(AG2_EXP_NABL & 4)
   if (threadIdx.x == 0) {
     const int t4 = (s_tot[0] + s_tot[1]) + (s_tot[2] + s_tot[3]);
     if (t4) atomicAdd(&st->sum_k1, (unsigned long long)t4);
   }
-#endif
 }
 
 int launch_normals(ag2_ctx* c) {

@@ -338,26 +338,8 @@ __global__ void __launch_bounds__(64) k_frames_finish(const HandConst* __restric
 // ---------------------------------------------------------------------------------------------
 // K3: hand sweep
 // ---------------------------------------------------------------------------------------------
-// phase stamps for the diagnostic build of the launch (thread 0 of each workgroup)
-// AG2_SWEEP_DIAG=1 (compile time, tools/ab_build.sh): pass A also counts its orientation-steps -- a branch per step
-// that costs the product kernel 2 us, so it is not compiled in by default
-#ifndef AG2_SWEEP_DIAG
-#define AG2_SWEEP_DIAG 0
-#endif
-#define AG2_PROF(i)                                                    \
-  do {                                                                 \
-    if (A.prof && tid == 0) {                                          \
-      const long long _t = clock64();                                  \
-      atomicAdd(&A.prof[i], (unsigned long long)(_t - tprev));         \
-      tprev = _t;                                                      \
-    }                                                                  \
-  } while (0)
-
 constexpr int kMaxPieces = 1024;
-#ifndef AG2_SWEEP_GROUP
-#define AG2_SWEEP_GROUP 8
-#endif
-constexpr int kGrp = AG2_SWEEP_GROUP;  // lanes that share one piece in the crop passes (tuning knob)
+constexpr int kGrp = 8;                // lanes that share one piece in the crop passes (tuning knob)
 constexpr int kGpw = kWave / kGrp;     // pieces per wave-wide load
 static_assert(kGrp >= 4 && kGrp <= 64 && (kGrp & (kGrp - 1)) == 0, "lane group must be a power of two");
 
@@ -504,7 +486,6 @@ k_sweep(SweepArgs A) {
   for (int w = blockIdx.x; w < n_work; w = next_work()) {
     if (tid == 0) nxt = gridDim.x + atomicAdd(&A.st->work_next[STAGE], 1u);
     const int t = (STAGE == 0) ? w : A.overflow[w];
-    long long tprev = A.prof ? clock64() : 0;
     if (!A.frame_ok[t]) continue;  // uniform
     const float4 q = A.sample_q[t];
     bool gmode = false;  // stage 0: this sample's list lives in the global slice (set once K is known)
@@ -641,7 +622,6 @@ k_sweep(SweepArgs A) {
       __syncthreads();
     }
     }
-    AG2_PROF(0);
 
     // ---- crop to the +-hand_height slab, ordered compaction --------------------------------
     const float cropn[3] = {(float)F[0][2], (float)F[1][2], (float)F[2][2]};
@@ -713,7 +693,6 @@ k_sweep(SweepArgs A) {
     my_k2 = wave_sum_i(my_k2);
     if (lane == 0) S.red.i[0][wid][0] = my_k2;
     __syncthreads();
-    AG2_PROF(1);
     // exclusive scan of the per-piece counts (thread t owns pieces 4t .. 4t+3)
     int k2 = 0;
     {
@@ -987,7 +966,6 @@ k_sweep(SweepArgs A) {
     }
     for (int e = tid; e < NW * kMaxOrient * 2; e += NT) (&S.exact_a[0][0][0])[e] = 0u;  // (read behind the barrier below)
     __syncthreads();
-    AG2_PROF(2);
 
     // ---- pass A for ALL orientations in one sweep over the LDS list -------------------------
     // evaluateFingers(points_rot, init_bite) (finger_hand.cpp:17-72) needs, per orientation, only
@@ -1075,14 +1053,8 @@ k_sweep(SweepArgs A) {
       const int n_it = (K + NT - 1) / NT;
       auto jof = [&](int sidx) { return sidx * NT + tid; };
       ldp(min(jof(0), K - 1), qx, qy, qz);
-#if AG2_SWEEP_DIAG
-      if (A.prof && lane == 0) atomicAdd(&A.prof[6], (unsigned long long)(n_it * R));
-#endif
       for (int sidx = 0; sidx < n_it; sidx++) {
         alive = (unsigned)__builtin_amdgcn_readfirstlane((int)(alive & ~S.dead));
-#if AG2_SWEEP_DIAG  // (orientation-steps done / possible, summed over waves: how early orientations retire)
-        if (A.prof && lane == 0) atomicAdd(&A.prof[4], (unsigned long long)__popc(alive));
-#endif
         if (alive == 0u) break;
         const int j = jof(sidx);
         const bool valid = j < K;
@@ -1182,7 +1154,6 @@ k_sweep(SweepArgs A) {
       }
     }
     __syncthreads();
-    AG2_PROF(3);
 
     // ---- orientations -----------------------------------------------------------------------
     // Lane i of every wave combines the waves' pass-A results for orientation i and applies the
@@ -1259,7 +1230,6 @@ k_sweep(SweepArgs A) {
         }
       }
     }
-    AG2_PROF(7);
   }
 }
 
@@ -1382,13 +1352,6 @@ int launch_sweep(ag2_ctx* c, size_t s, uint64_t slot_base, bool emit_lists, bool
   A.overflow = c->d_overflow.as<int>();
   A.min_z = c->min_z;
   A.flags = c->p.debug_flags & 1;
-  DevBuf& prof_buf = c->d_sweep_prof;  // diagnostic only: per-phase cycle sums when AG2_SWEEP_PROF is set
-  const bool want_prof = !c->fm_on && getenv("AG2_SWEEP_PROF") != nullptr;
-  if (want_prof) {
-    AG2_HIP(c, prof_buf.reserve(16 * 8));
-    AG2_HIP(c, hipMemsetAsync(prof_buf.p, 0, 16 * 8, c->stream));
-    A.prof = prof_buf.as<unsigned long long>();
-  }
   const size_t lds = sweep_lds_bytes(0);
   typedef void (*SweepFn)(SweepArgs);
   const SweepFn fn_lds = (R <= 8) ? k_sweep<0, 8> : (R <= 16 ? k_sweep<0, 16> : k_sweep<0, 32>);
@@ -1409,15 +1372,6 @@ int launch_sweep(ag2_ctx* c, size_t s, uint64_t slot_base, bool emit_lists, bool
   hipLaunchKernelGGL(fn_lds, dim3(grid), dim3(kSweepThreads0), lds, c->stream, A);
   AG2_HIP(c, hipGetLastError());
   AG2_HIP(c, stage_event(c, 2));
-  if (want_prof) {
-    unsigned long long h[8];
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
-    AG2_HIP(c, hipMemcpy(h, prof_buf.p, sizeof(h), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[ag2 sweep prof, stage 0, cycles summed over workgroups] rows %llu crop1 %llu "
-            "crop2 %llu passA %llu other %llu | pass A orientation-steps done %llu of %llu\n",
-            h[0], h[1], h[2], h[3], h[7], h[4], h[6]);
-    AG2_HIP(c, hipMemsetAsync(prof_buf.p, 0, 16 * 8, c->stream));
-  }
   // Samples whose cropped list exceeds stage 0 were queued on the device; the second stage is always
   // launched and reads the queue length itself (st->n_overflow), so no host round trip sits between
   // the launches.
@@ -1438,14 +1392,6 @@ int launch_sweep(ag2_ctx* c, size_t s, uint64_t slot_base, bool emit_lists, bool
     if (rc) return rc;
   }
   AG2_HIP(c, stage_event(c, 11));
-  if (want_prof) {
-    unsigned long long h[8];
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
-    AG2_HIP(c, hipMemcpy(h, prof_buf.p, sizeof(h), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[ag2 sweep prof, stage 1 (global scratch)] rows %llu crop1 %llu crop2 %llu passA %llu "
-            "deepen %llu passC %llu passD %llu other %llu\n",
-            h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-  }
   return 0;
 }
 

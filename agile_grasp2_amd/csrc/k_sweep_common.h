@@ -50,7 +50,6 @@ struct SweepArgs {
   int gpos_cap;              // ... the longest list stage 0 keeps; longer ones go to the long-list stage
   float min_z;
   int flags;                 // bit0: no row tightening (exact K2 accounting, diagnostic)
-  unsigned long long* prof;  // optional per-phase cycle sums (AG2_SWEEP_PROF=1), else nullptr
   // split sweep: the first kernels stop at the gates and queue (sample, orientation) pairs for
   // k_sweep_orient, with the sample's cropped list in the list arena: one float4 per point, the
   // centred coordinates p - q (float, the value the crop computed) and the sorted position as bits
