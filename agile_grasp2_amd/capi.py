@@ -30,6 +30,8 @@ SYMBOLS = [
     "ag2_submit_frame", "ag2_submit_frame_raw", "ag2_wait_frame", "ag2_pipe_create", "ag2_pipe_destroy",
     "ag2_pipe_last_error", "ag2_pipe_context", "ag2_pipe_lenet_load", "ag2_pipe_submit", "ag2_pipe_submit_raw",
     "ag2_pipe_wait", "ag2_set_wait_mode", "ag2_get_wait_info",
+    "ag2_default_importance_params", "ag2_detect_importance", "ag2_get_importance_rounds", "ag2_get_importance_info",
+    "ag2_importance_sample",
 ]
 
 
@@ -73,6 +75,31 @@ class WaitInfo(C.Structure):
                                           "last_wait_us")]
 
 
+IS_SUM, IS_MAX = 1, 2
+IMPORTANCE_MAX_ROUNDS = 64
+IMPORTANCE_MAX_HANDS = 8192
+
+
+class ImportanceParams(C.Structure):
+    _fields_ = [("num_iterations", C.c_int32), ("num_samples", C.c_int32), ("prob_rand_samples", C.c_double),
+                ("radius", C.c_double), ("method", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ImportanceInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in (
+        "host_syncs", "one_trip", "redone", "n_initial", "rounds", "num_samples", "n_hands", "n_out")] + [
+        ("tried", C.c_int64 * IMPORTANCE_MAX_ROUNDS), ("accepted", C.c_int64 * IMPORTANCE_MAX_ROUNDS)]
+
+
+def default_importance_params(**kw) -> ImportanceParams:
+    """ag2_default_importance_params (importance_sampling.cpp:9-15), then the keyword overrides."""
+    p = ImportanceParams()
+    load().ag2_default_importance_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class Times(C.Structure):
     _fields_ = [(n, C.c_float) for n in (
         "grid_ms", "normals_ms", "frames_ms", "sweep_ms", "compact_ms", "render_ms",
@@ -107,6 +134,8 @@ def load():
     L.ag2_last_error.restype = C.c_char_p
     L.ag2_last_error.argtypes = [C.c_void_p]
     L.ag2_default_params.argtypes = [C.POINTER(Params)]
+    L.ag2_default_importance_params.restype = None
+    L.ag2_default_importance_params.argtypes = [C.c_void_p]
     L.ag2_pipe_create.restype = C.c_void_p
     L.ag2_pipe_create.argtypes = [C.POINTER(Params), C.c_int, C.c_int]
     L.ag2_pipe_destroy.argtypes = [C.c_void_p]
@@ -374,6 +403,55 @@ class Detector:
                                    _ptr(allh) if want_all else None,
                                    C.c_size_t(cap if want_all else 0), C.byref(na)))
         return sel[: ns.value].copy(), (allh[: na.value].copy() if want_all else na.value)
+
+    def detect_importance(self, sample_idx=None, seed=0, do_prune=True, params: ImportanceParams | None = None,
+                          cap=None, n_resident=None, **kw):
+        """ImportanceSampling::detectGraspPoses on the device: (hands, rounds) -- rounds is a list of 3 x num_samples
+        arrays, one per round.  kw: fields of ImportanceParams.  cap: size of the output buffer (default: enough)."""
+        ip = params if params is not None else default_importance_params(**kw)
+        if n_resident is not None:  # indices left on the device by subsample_uniformly
+            si, s = None, int(n_resident)
+        else:
+            si = np.ascontiguousarray(sample_idx, dtype=np.int32)
+            s = si.shape[0]
+        nsel = int(self.params.num_selected)
+        per = s * int(self.params.num_orientations)
+        if cap is None:
+            k0 = per if nsel < 0 else min(per, nsel)
+            kr = ip.num_samples * int(self.params.num_orientations)
+            cap = k0 + ip.num_iterations * (kr if nsel < 0 else min(kr, nsel))
+        out = np.zeros(max(1, cap), dtype=HYP_DTYPE)
+        n = C.c_size_t(0)
+        self._ck(self.L.ag2_detect_importance(self.h, _ptr(si), C.c_size_t(s), C.c_uint64(seed),
+                                              C.c_int(1 if do_prune else 0), C.byref(ip), _ptr(out),
+                                              C.c_size_t(cap), C.byref(n)))
+        return out[: n.value].copy(), self.importance_rounds(ip.num_samples)
+
+    def importance_sample(self, surfaces, round_: int, seed=0, params: ImportanceParams | None = None, **kw):
+        """One round of the sampler on the given hand surfaces (3 x h): (xyz 3 x num_samples, tried, accepted)."""
+        ip = params if params is not None else default_importance_params(**kw)
+        srf = np.asfortranarray(np.asarray(surfaces, dtype=np.float64))
+        assert srf.shape[0] == 3
+        xyz = np.zeros((3, ip.num_samples), dtype=np.float64, order="F")
+        tried, acc = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.ag2_importance_sample(self.h, _ptr(srf), C.c_size_t(srf.shape[1]), C.byref(ip),
+                                              C.c_int(round_), C.c_uint64(seed), _ptr(xyz), C.byref(tried),
+                                              C.byref(acc)))
+        return xyz, tried.value, acc.value
+
+    def importance_rounds(self, num_samples: int):
+        """The samples of the last detect_importance call: a list of 3 x num_samples arrays."""
+        n = C.c_size_t(0)
+        self._ck(self.L.ag2_get_importance_rounds(self.h, None, C.c_size_t(0), C.byref(n)))  # (the size)
+        buf = np.zeros(max(1, n.value), dtype=np.float64)
+        self._ck(self.L.ag2_get_importance_rounds(self.h, _ptr(buf), C.c_size_t(len(buf)), C.byref(n)))
+        per = 3 * num_samples
+        return [buf[k * per:(k + 1) * per].reshape(num_samples, 3).T.copy() for k in range(n.value // per)]
+
+    def importance_info(self) -> ImportanceInfo:
+        i = ImportanceInfo()
+        self._ck(self.L.ag2_get_importance_info(self.h, C.byref(i)))
+        return i
 
     def stream_configure(self, max_points=0, max_samples=0, use_graph=True):
         self._ck(self.L.ag2_stream_configure(self.h, C.c_size_t(max_points), C.c_size_t(max_samples),

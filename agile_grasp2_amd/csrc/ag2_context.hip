@@ -104,11 +104,11 @@ int collect_normals_stats(ag2_ctx* c) {
     c->grid_pending = false;
   }
   if (!c->normals_pending) return 0;
-  if (stage_event_on(c, 10)) AG2_HIP(c, hipEventSynchronize(c->ev[10]));
-  else AG2_HIP(c, hipStreamSynchronize(c->stream));  // k_normals must be done before its counter is read
+  if (stage_event_on(c, 10)) AG2_HIP(c, ag2::event_sync(c, c->ev[10]));
+  else AG2_HIP(c, ag2::stream_sync(c));  // k_normals must be done before its counter is read
   stage_elapsed(c, &c->times.normals_ms, 9, 10);
   unsigned long long k1 = 0;
-  AG2_HIP(c, hipMemcpy(&k1, (const char*)c->d_stats.p + offsetof(DevStats, sum_k1), 8, hipMemcpyDeviceToHost));
+  AG2_HIP(c, ag2::sync_copy(c, &k1, (const char*)c->d_stats.p + offsetof(DevStats, sum_k1), 8, hipMemcpyDeviceToHost));
   c->cnt.sum_k1 = (int64_t)k1;
   c->normals_pending = false;
   return 0;
@@ -118,7 +118,7 @@ int pin_reserve(ag2_ctx* c, size_t bulk_bytes) {
   const size_t need = kPinSmall + bulk_bytes;
   if (need <= c->h_pin_bytes) return 0;
   // (unconditional: a NULL handle is the HIP default stream, a supported setting -- ag2_set_stream)
-  AG2_HIP(c, hipStreamSynchronize(c->stream));  // nothing may still be copying
+  AG2_HIP(c, ag2::stream_sync(c));  // nothing may still be copying
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   c->h_pin = nullptr;
   c->h_pin_dev = nullptr;
@@ -243,7 +243,7 @@ ag2_ctx* ag2_create(const ag2_params* p, int device_id) {
 void ag2_destroy(ag2_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);  // NULL = the default stream: still to be waited for
+  (void)ag2::stream_sync(c);  // NULL = the default stream: still to be waited for
   frame_release(c);
   DevBuf* bufs[] = {&c->d_griddesc, &c->d_lists, &c->d_pairs, &c->d_obox, &c->d_xyz_in, &c->d_key, &c->d_bounds, &c->d_gpos, &c->d_export_list, &c->d_cell, &c->d_perm, &c->d_sorted,
                     &c->d_nrm, &c->d_scan, &c->d_stats, &c->d_hc, &c->d_sample_q, &c->d_frames,
@@ -267,7 +267,7 @@ const char* ag2_last_error(const ag2_ctx* c) { return c ? c->err.c_str() : "null
 int ag2_set_stream(ag2_ctx* c, void* hip_stream) {
   if (!c) return AG2_ERR_ARG;
   (void)hipSetDevice(c->device);
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   c->own_stream = false;
   c->stream = (hipStream_t)hip_stream;  // NULL = the HIP default (null) stream, torch's default
@@ -301,7 +301,7 @@ int ag2_set_cloud(ag2_ctx* c, const float* xyz, size_t n, size_t stride_bytes,
   }
   AG2_HIP(c, c->d_xyz_in.reserve(std::max<size_t>(n, 1) * 16));
   if (n) AG2_HIP(c, hipMemcpyAsync(c->d_xyz_in.p, pack.data(), n * 16, hipMemcpyHostToDevice, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   int rc = after_cloud(c);
   if (rc) return rc;
   if (normals && c->n_valid) {
@@ -316,7 +316,7 @@ int ag2_set_cloud(ag2_ctx* c, const float* xyz, size_t n, size_t stride_bytes,
     AG2_HIP(c, hipMemcpyAsync(c->d_tmp.p, nf.data(), n * 16, hipMemcpyHostToDevice, c->stream));
     rc = gather_normals(c);
     if (rc) return rc;
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
     c->has_normals = true;
   }
   return 0;
@@ -368,7 +368,7 @@ int ag2_get_normals(ag2_ctx* c, double* out) {
   std::vector<int32_t> perm(c->n_valid);
   AG2_HIP(c, hipMemcpyAsync(nf.data(), c->d_nrm.p, c->n_valid * 16, hipMemcpyDeviceToHost, c->stream));
   AG2_HIP(c, hipMemcpyAsync(perm.data(), c->d_perm.p, c->n_valid * 4, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   for (size_t pos = 0; pos < c->n_valid; pos++) {
     const size_t i = (size_t)perm[pos];
     out[3 * i] = (double)nf[4 * pos];
@@ -386,7 +386,7 @@ int ag2_get_grid_perm(ag2_ctx* c, int32_t* perm, size_t cap, size_t* n_valid) {
   if (cap < c->n_valid) return set_err(c, AG2_ERR_CAPACITY, "perm buffer too small");
   if (c->n_valid) {  // ordered behind the grid kernels on the context's stream
     AG2_HIP(c, hipMemcpyAsync(perm, c->d_perm.p, c->n_valid * 4, hipMemcpyDeviceToHost, c->stream));
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
   }
   return 0;
 }
@@ -395,7 +395,7 @@ int ag2_set_stage_timing(ag2_ctx* c, int level) {
   if (!c) return AG2_ERR_ARG;
   if (level < 0 || level > 2) return set_err(c, AG2_ERR_ARG, "stage timing level must be 0, 1 or 2");
   (void)hipSetDevice(c->device);
-  AG2_HIP(c, hipStreamSynchronize(c->stream));  // no half-recorded pairs
+  AG2_HIP(c, ag2::stream_sync(c));  // no half-recorded pairs
   c->stage_timing = level;
   memset(&c->times, 0, sizeof(c->times));
   c->grid_pending = false;  // (its events may not exist at the new level)

@@ -186,13 +186,14 @@ __global__ void __launch_bounds__(kTopkThreads) k_topk(const ag2_hypothesis* __r
 // sequence number (the kernel that writes it has finished): anything else is reported, not ignored.
 int wait_flag(ag2_ctx* c, size_t flag_off, unsigned want) {
   if (!c->h_pin_dev) {
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
     return 0;
   }
   return wait_flag_at(c, reinterpret_cast<const volatile unsigned*>(pin_small(c) + flag_off), want);
 }
 int wait_flag_at(ag2_ctx* c, const volatile unsigned* flag, unsigned want) {
   if (c->wait_poll && flag) {
+    c->host_waits++;
     const auto t0 = std::chrono::steady_clock::now();
     const auto spin_for = std::chrono::microseconds(c->wait_spin_us);
     bool yielding = false;
@@ -214,7 +215,7 @@ int wait_flag_at(ag2_ctx* c, const volatile unsigned* flag, unsigned want) {
     }
     c->poll_fallbacks++;
   }
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   if (c->wait_poll && flag && *flag != want)
     return set_err(c, AG2_ERR_STATE, "the stream is idle but the kernel's flag does not hold the call's sequence number (have " +
                                          std::to_string(*flag) + ", want " + std::to_string(want) + ")");
@@ -245,12 +246,12 @@ int frame_pin_reserve(ag2_ctx* c, ag2_frame_state* f) {
   f->off_rec = off_rec;
   if (need <= f->h_pin_bytes) {
     if (moved) {  // the results' place holds something else: below every sequence number before it is polled
-      AG2_HIP(c, hipStreamSynchronize(c->stream));
+      AG2_HIP(c, ag2::stream_sync(c));
       reinterpret_cast<FrameOut*>(f->h_pin + off_out)->done_seq = 0u;
     }
     return 0;
   }
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   if (f->h_pin) (void)hipHostFree(f->h_pin);
   f->h_pin = nullptr;
   f->h_pin_bytes = 0;
@@ -561,7 +562,7 @@ int frame_submit_impl(ag2_ctx* c, const FrameIn& in) {
   if (!in.on_device && n) {
     const size_t bytes = n * in.stride;
     if (bytes > f->h_stage_bytes) {
-      AG2_HIP(c, hipStreamSynchronize(c->stream));
+      AG2_HIP(c, ag2::stream_sync(c));
       if (f->h_stage) (void)hipHostFree(f->h_stage);
       f->h_stage = nullptr;
       f->h_stage_bytes = 0;
@@ -702,7 +703,7 @@ int frame_wait_impl(ag2_ctx* c, ag2_hypothesis* selected, size_t cap, size_t* n_
           const unsigned long long sig0 = frame_signature(c, f);
           const int lvl = c->stage_timing;
           c->stage_timing = 0;
-          (void)hipStreamSynchronize(c->stream);  // (the results were polled for: let the runtime see the stream idle)
+          (void)ag2::stream_sync(c);  // (the results were polled for: let the runtime see the stream idle)
           hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
           int rc2 = (e == hipSuccess) ? enqueue_frame(c, f, in.do_prune) : AG2_ERR_HIP;
           hipGraph_t g = nullptr;
@@ -712,7 +713,7 @@ int frame_wait_impl(ag2_ctx* c, ag2_hypothesis* selected, size_t cap, size_t* n_
               hipGraphInstantiate(&f->exec, g, nullptr, nullptr, 0) == hipSuccess) {
             // (the executable graph's first launch would otherwise carry its upload to the device)
             (void)hipGraphUpload(f->exec, c->stream);
-            (void)hipStreamSynchronize(c->stream);
+            (void)ag2::stream_sync(c);
             f->graph = g;
             f->graph_valid = true;
             f->sig_at_capture = sig0;
@@ -838,7 +839,7 @@ int ag2_stream_configure(ag2_ctx* c, size_t max_points, size_t max_samples, int 
   (void)hipSetDevice(c->device);
   if (!c->fm) c->fm = new ag2_frame_state();
   ag2_frame_state* f = c->fm;
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   drop_graph(f);
   f->use_graph = use_graph != 0;
   f->shapes_known = false;

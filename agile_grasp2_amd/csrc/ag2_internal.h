@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -10,12 +11,17 @@
 
 namespace ag2 {
 
+// hipFree calls of the library, process-wide: hipFree waits for the device, so each is a host wait that no
+// stream synchronisation shows (ag2_get_importance_info counts them into host_syncs)
+inline std::atomic<unsigned long long> g_buffer_frees{0};
+
 // Grow-only device buffer.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
   hipError_t reserve(size_t need) {
     if (need <= bytes) return hipSuccess;
+    if (p) g_buffer_frees++;
     if (p) (void)hipFree(p);
     p = nullptr;
     bytes = 0;
@@ -287,12 +293,44 @@ struct ag2_ctx {
   int64_t poll_yields = 0;      // sched_yield calls of those waits
   int64_t last_wait_us = 0, last_submit_us = 0;  // host time inside the last frame_wait / frame_submit
 
+  // ag2_detect_importance (ag2_importance.hip)
+  bool queries_preset = false;  // the sample query points are already in d_sample_q (written by the IS sampler)
+  ag2::DevBuf d_is;             // result block of a call: per-detect statistics, per-round samples, the hand list
+  ag2::DevBuf d_is_samp;        // ag2_importance_sample: hand surfaces in, one round's samples out
+  struct IsShapes {             // shapes the queued form runs at, learned from the previous call
+    bool valid = false;
+    size_t s = 0;
+    int num_samples = 0, rounds = 0, prune = -1;
+    size_t cap_img0 = 0, cap_img_r = 0;  // images of the initial detect / of a round
+    int max_p = 0;
+  } is_shapes;
+  ag2_importance_info is_info{};
+  std::vector<double> is_rounds;  // the last call's samples, round-major
+
+  // every wait of the host for this context's work: stream / event synchronisations, synchronous copies, flag polls
+  // (ag2::stream_sync and its siblings below count them)
+  unsigned long long host_waits = 0;
+
   ag2::LeNetDev net;
   ag2_counters cnt{};
   ag2_times times{};
 };
 
 namespace ag2 {
+
+// The host's waits for a context, counted (ag2_ctx::host_waits).
+inline hipError_t stream_sync(ag2_ctx* c) {
+  c->host_waits++;
+  return hipStreamSynchronize(c->stream);
+}
+inline hipError_t event_sync(ag2_ctx* c, hipEvent_t e) {
+  c->host_waits++;
+  return hipEventSynchronize(e);
+}
+inline hipError_t sync_copy(ag2_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  c->host_waits++;
+  return hipMemcpy(dst, src, bytes, kind);
+}
 
 int set_err(ag2_ctx* c, int code, const std::string& msg);
 enum { kAttrRender = 1u, kAttrLenetConv = 2u, kAttrLenetX3 = 4u, kAttrLenetX3b = 8u };
@@ -343,7 +381,7 @@ inline void stage_elapsed(ag2_ctx* c, float* ms, int a, int b) {
   }
 }
 inline hipError_t stage_sync(ag2_ctx* c, int i) {
-  return stage_event_on(c, i) ? hipEventSynchronize(c->ev[i]) : hipSuccess;
+  return stage_event_on(c, i) ? ag2::event_sync(c, c->ev[i]) : hipSuccess;
 }
 int gather_normals(ag2_ctx* c);  // d_tmp (float4, original order) -> d_nrm (sorted order)
 int pack_device_xyz(ag2_ctx* c, const void* d_xyz, size_t n, size_t stride_bytes, float4* dst,
@@ -417,6 +455,23 @@ int launch_lenet_conv_x3(ag2_ctx* c, const uint8_t* d_images, size_t n, float* d
 int lenet_pack_fc_x3(ag2_ctx* c, const float* w3p_7200x512);
 int launch_lenet_fc1_x3(ag2_ctx* c, size_t n, int* n_pad_out, int* ksplit_out,
                         const unsigned* d_n = nullptr);
+// ag2_pipeline.hip: frames + sweep + prune compaction of one detect queued without a host wait (statistics stay on
+// the device); sample_idx == NULL with c->queries_preset: the query points are already in d_sample_q
+int enqueue_hypotheses(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint64_t seed, int do_prune);
+// ... and the counters / stage times such a detect leaves once the stream has been waited for (its statistics hs)
+void note_detect_stats(ag2_ctx* c, size_t s, const DevStats& hs, size_t n_selected);
+// k_importance.hip: one round of the importance sampler, one workgroup
+struct IsRound {
+  int method;                   // AG2_IS_SUM / AG2_IS_MAX
+  double sigma, term, coef;     // radius, 1 / sqrt((2 pi)^3 sigma^3), -1 / (2 sigma)
+  uint64_t seed, stream;        // stream 0xFFFFFFFFFFFF0000 + round
+  int num_samples, num_gauss;
+};
+// hand h's surface: d_srf[h * stride .. + 2] (ag2_hypothesis records: their surface member, stride 22 doubles)
+int launch_is_sample(ag2_ctx* c, const double* d_srf, int stride, const unsigned* d_nh, const IsRound& r,
+                     double* d_xyz, float4* d_q, long long* d_info);
+int launch_is_append(ag2_ctx* c, const FrameOut* d_fo, const ag2_hypothesis* d_rec, ag2_hypothesis* d_hands,
+                     unsigned* d_nh, unsigned cap);
 // k_cluster.hip
 int cluster_async(ag2_ctx* c, const ag2_hypothesis* d_in, size_t n_max, const unsigned* d_n,
                   int min_inliers, unsigned* d_count);

@@ -42,7 +42,7 @@ __global__ void k_export_table(const uint4* __restrict__ table, const unsigned c
 
 int read_stats(ag2_ctx* c, DevStats* hs) {
   AG2_HIP(c, hipMemcpyAsync(pin_small(c), c->d_stats.p, sizeof(DevStats), hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   memcpy(hs, pin_small(c), sizeof(DevStats));
   return 0;
 }
@@ -93,7 +93,7 @@ int run_hypotheses(ag2_ctx* c, const int32_t* sample_idx, const double* sample_x
   for (int attempt = 0; attempt < 6; attempt++) {
     // with index samples the kernel that fetches them also clears the slot states and the per-run
     // statistics (two fills less)
-    const bool fused_clear = s > 0 && (sample_idx || !sample_xyz);
+    const bool fused_clear = s > 0 && !c->queries_preset && (sample_idx || !sample_xyz);
     int rc = 0;
     if (fused_clear)
       AG2_HIP(c, c->d_tab_keep.reserve(std::max<size_t>(s * (size_t)c->p.num_orientations, 1)));
@@ -229,7 +229,7 @@ int detect_speculative(ag2_ctx* c, const int32_t* sample_idx, const double* samp
   if (rc) return rc;
   AG2_HIP(c, stage_event(c, 7));
   if (c->stage_timing >= 2) {  // (event 7 is behind k_topk: wait for the stream)
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
   } else {
     rc = wait_topk(c);
     if (rc) return rc;
@@ -269,12 +269,29 @@ int detect_speculative(ag2_ctx* c, const int32_t* sample_idx, const double* samp
 }  // namespace
 
 namespace ag2 {
+int enqueue_hypotheses(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint64_t seed, int do_prune) {
+  return run_hypotheses(c, sample_idx, nullptr, s, 0, seed, true, do_prune ? 1 : 0, /*defer_read=*/true);
+}
+
+void note_detect_stats(ag2_ctx* c, size_t s, const DevStats& hs, size_t n_selected) {
+  note_sweep(c, s, hs, 1);
+  c->cnt.n_pruned = (int64_t)hs.n_list;
+  c->cnt.n_scored = (int64_t)hs.n_list;
+  c->cnt.n_selected = (int64_t)n_selected;
+  stage_elapsed(c, &c->times.compact_ms, 11, 3);
+  stage_elapsed(c, &c->times.render_ms, 3, 4);
+  stage_elapsed(c, &c->times.lenet_conv_ms, 4, 5);
+  stage_elapsed(c, &c->times.lenet_fc_ms, 5, 6);
+  stage_elapsed(c, &c->times.select_ms, 6, 7);
+  stage_elapsed(c, &c->times.total_ms, 8, 7);
+}
+
 // Takes up what a rank's one-trip detect left: the statistics k_export_selected copied into page-locked memory
 // (counters, stage times, the shapes the next call is launched at).  Called where the stream has been waited
 // for anyway (merge, gather); elsewhere (stream_is_idle == false) it waits itself.
 int rank_spec_collect(ag2_ctx* c, bool stream_is_idle) {
   if (!c->rank_spec.pending) return 0;
-  if (!stream_is_idle) AG2_HIP(c, hipStreamSynchronize(c->stream));
+  if (!stream_is_idle) AG2_HIP(c, ag2::stream_sync(c));
   c->rank_spec.pending = false;
   DevStats hs;
   memcpy(&hs, pin_small(c) + kPinRankStats, sizeof(hs));
@@ -321,7 +338,7 @@ int ag2_local_frames(ag2_ctx* c, const int32_t* sample_idx, const double* sample
   if (s) {
     AG2_HIP(c, hipMemcpyAsync(frames, c->d_frames.p, s * 96, hipMemcpyDeviceToHost, c->stream));
     AG2_HIP(c, hipMemcpyAsync(valid, c->d_frame_ok.p, s * 4, hipMemcpyDeviceToHost, c->stream));
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
     for (size_t i = 0; i < s; i++)
       if (!valid[i])
         for (int k = 0; k < 12; k++) frames[12 * i + k] = 0.0;
@@ -347,7 +364,7 @@ int ag2_generate_hypotheses(ag2_ctx* c, const int32_t* sample_idx, const double*
   c->h_keep = keep;
   c->h_slots.resize(nh);
   if (nh) {
-    AG2_HIP(c, hipMemcpy(c->h_slots.data(), c->d_list.p, nh * 4, hipMemcpyDeviceToHost));
+    AG2_HIP(c, ag2::sync_copy(c, c->h_slots.data(), c->d_list.p, nh * 4, hipMemcpyDeviceToHost));
   }
   *n_out = nh;
   if (nh > cap) return set_err(c, AG2_ERR_CAPACITY, "generate_hypotheses: output capacity too small");
@@ -363,7 +380,7 @@ int ag2_hyp_points(ag2_ctx* c, size_t h, double* pts, double* nrm) {
   const int64_t off = c->h_offsets[h];
   if (off < 0) return set_err(c, AG2_ERR_STATE, "no point list stored for this hypothesis");
   std::vector<double> buf((size_t)P * 6);
-  AG2_HIP(c, hipMemcpy(buf.data(), c->d_arena.as<double>() + (size_t)off * 6, (size_t)P * 48,
+  AG2_HIP(c, ag2::sync_copy(c, buf.data(), c->d_arena.as<double>() + (size_t)off * 6, (size_t)P * 48,
                        hipMemcpyDeviceToHost));
   for (int b = 0; b < P; b++)
     for (int k = 0; k < 3; k++) {
@@ -395,7 +412,7 @@ int ag2_render_images(ag2_ctx* c, size_t first, size_t count, uint8_t* out) {
   if (rc) return rc;
   AG2_HIP(c, stage_event(c, 4));
   AG2_HIP(c, hipMemcpyAsync(out, c->d_images.p, count * 10800, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   stage_elapsed(c, &c->times.render_ms, 3, 4);
   return 0;
 }
@@ -431,7 +448,7 @@ int ag2_render_images_from_points(ag2_ctx* c, size_t n, const int64_t* offsets, 
   const int rc = launch_render(c, c->d_tmp.as<double>(), d_off, d_cnt, n, c->d_images.as<uint8_t>(), max_p);
   if (rc) return rc;
   AG2_HIP(c, hipMemcpyAsync(out, c->d_images.p, n * 10800, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   return 0;
 }
 
@@ -460,7 +477,7 @@ int ag2_lenet_forward(ag2_ctx* c, const uint8_t* images, size_t n, float* out) {
   if (rc) return rc;
   AG2_HIP(c, stage_event(c, 6));
   AG2_HIP(c, hipMemcpyAsync(out, c->d_logits.p, n * 8, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   stage_elapsed(c, &c->times.lenet_conv_ms, 4, 5);
   stage_elapsed(c, &c->times.lenet_fc_ms, 5, 6);
   return 0;
@@ -568,16 +585,16 @@ int ag2_detect(ag2_ctx* c, const int32_t* sample_idx, const double* sample_xyz, 
       rc = pin_reserve(c, rec_bytes + 16);
       if (rc) return rc;
       AG2_HIP(c, hipMemcpyAsync(pin_bulk(c), d_res, rec_bytes + 4, hipMemcpyDeviceToHost, c->stream));
-      AG2_HIP(c, hipStreamSynchronize(c->stream));
+      AG2_HIP(c, ag2::stream_sync(c));
       memcpy(&n_anti, pin_bulk(c) + rec_bytes, 4);
       recs = (const ag2_hypothesis*)pin_bulk(c);  // (nothing below writes the staging area)
     } else {
       AG2_HIP(c, hipMemcpyAsync(pin_small(c), d_nres, 4, hipMemcpyDeviceToHost, c->stream));
-      AG2_HIP(c, hipStreamSynchronize(c->stream));
+      AG2_HIP(c, ag2::stream_sync(c));
       memcpy(&n_anti, pin_small(c), 4);
       anti.resize(n_anti);
       if (n_anti)
-        AG2_HIP(c, hipMemcpy(anti.data(), d_res, (size_t)n_anti * sizeof(ag2_hypothesis),
+        AG2_HIP(c, ag2::sync_copy(c, anti.data(), d_res, (size_t)n_anti * sizeof(ag2_hypothesis),
                              hipMemcpyDeviceToHost));
       recs = anti.data();
     }
@@ -605,7 +622,7 @@ int ag2_detect(ag2_ctx* c, const int32_t* sample_idx, const double* sample_xyz, 
     if (rc) return rc;
     if (n_img) memcpy(scored_all, all.data(), n_img * sizeof(ag2_hypothesis));
   }
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   stage_elapsed(c, &c->times.compact_ms, 11, 3);
   stage_elapsed(c, &c->times.render_ms, 3, 4);
   stage_elapsed(c, &c->times.lenet_conv_ms, 4, 5);
@@ -641,7 +658,7 @@ int ag2_export_selected_compact_device(ag2_ctx* c, void* d_dst, size_t bytes, si
   if (!c->d_last_sel || cap_records == 0) {  // a detect over no images: an empty list
     const unsigned hdr[4] = {0u, (unsigned)cap_records, 0u, 0u};
     AG2_HIP(c, hipMemcpyAsync(d_dst, hdr, 16, hipMemcpyHostToDevice, c->stream));
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
     return 0;
   }
   return export_selected_compact(c, d_dst, cap_records);
@@ -660,7 +677,7 @@ int ag2_gather_begin(ag2_ctx* root, size_t world, size_t cap_records) {
   (void)hipSetDevice(root->device);
   if (world > 4096 || cap_records > ((size_t)1 << 24)) return set_err(root, AG2_ERR_ARG, "gather: sizes");
   const size_t per = 16 + cap_records * sizeof(ag2_hypothesis);
-  AG2_HIP(root, hipStreamSynchronize(root->stream));  // (a merge of the previous exchange may still read the buffer)
+  AG2_HIP(root, ag2::stream_sync(root));  // (a merge of the previous exchange may still read the buffer)
   AG2_HIP(root, root->d_gather.reserve(world * per));
   // No rank has delivered yet, and the merge refuses to run while one is missing: a rank that failed can no longer
   // leave the previous exchange's records in its place.  (Clearing the headers as well would cost a
@@ -684,7 +701,7 @@ int ag2_gather_selected(ag2_ctx* root, ag2_ctx* src, size_t rank) {
     AG2_HIP(src, hipMemcpyAsync(dst, src->d_xchg.p, per, hipMemcpyDeviceToDevice, src->stream));
   else  // over xGMI; the runtime stages through the host when the devices have no peer access
     AG2_HIP(src, hipMemcpyPeerAsync(dst, root->device, src->d_xchg.p, src->device, per, src->stream));
-  AG2_HIP(src, hipStreamSynchronize(src->stream));
+  AG2_HIP(src, ag2::stream_sync(src));
   {  // (the stream is idle: what a one-trip rank detect left is taken up here)
     const int rcc = rank_spec_collect(src, /*stream_is_idle=*/true);
     if (rcc) return rcc;

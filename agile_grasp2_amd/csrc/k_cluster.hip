@@ -173,11 +173,11 @@ int ag2_find_clusters(ag2_ctx* c, const ag2_hypothesis* hands, size_t n, int min
   if (rc) return rc;
   unsigned k = 0;
   AG2_HIP(c, hipMemcpyAsync(&k, d_n + 1, 4, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   *n_out = k;
   if (k > cap) return set_err(c, AG2_ERR_CAPACITY, "find_clusters: output capacity too small");
   if (k && !out) return set_err(c, AG2_ERR_ARG, "find_clusters: out is NULL");
-  if (k) AG2_HIP(c, hipMemcpy(out, c->d_cluster.p, (size_t)k * sizeof(ag2_hypothesis), hipMemcpyDeviceToHost));
+  if (k) AG2_HIP(c, ag2::sync_copy(c, out, c->d_cluster.p, (size_t)k * sizeof(ag2_hypothesis), hipMemcpyDeviceToHost));
   return 0;
 }
 

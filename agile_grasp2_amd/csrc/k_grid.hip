@@ -548,13 +548,13 @@ int build_grid(ag2_ctx* c) {
         const int rcw = wait_flag(c, kPinBoundsFlag, c->bounds_seq);
         if (rcw) return rcw;
       } else {
-        AG2_HIP(c, hipStreamSynchronize(c->stream));
+        AG2_HIP(c, ag2::stream_sync(c));
       }
       c->bounds_flag_armed = false;
     } else {
       AG2_HIP(c, hipMemcpyAsync(pin_small(c), c->d_bounds.p, (size_t)nb * 32, hipMemcpyDeviceToHost,
                                 c->stream));
-      AG2_HIP(c, hipStreamSynchronize(c->stream));
+      AG2_HIP(c, ag2::stream_sync(c));
     }
     c->bounds_in_pin = false;
     const int* part = (const int*)pin_small(c);

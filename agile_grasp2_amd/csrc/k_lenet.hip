@@ -326,7 +326,7 @@ int lenet_pack_weights(ag2_ctx* c, const float* c1w, const float* c1b, const flo
     AG2_HIP(c, u.b->reserve(u.n * 4));
     AG2_HIP(c, hipMemcpyAsync(u.b->p, u.p, u.n * 4, hipMemcpyHostToDevice, c->stream));
   }
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   int rc = lenet_pack_weights_x3(c, c1w, c2w);
   if (rc) return rc;
   rc = lenet_pack_fc_x3(c, w3p.data());

@@ -553,7 +553,7 @@ int lenet_pack_weights_x3(ag2_ctx* c, const float* c1w, const float* c2w) {
   AG2_HIP(c, d.w2x.reserve(w2x.size() * 2));
   AG2_HIP(c, hipMemcpyAsync(d.w1x.p, w1x.data(), w1x.size() * 2, hipMemcpyHostToDevice, c->stream));
   AG2_HIP(c, hipMemcpyAsync(d.w2x.p, w2x.data(), w2x.size() * 2, hipMemcpyHostToDevice, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   return 0;
 }
 
@@ -732,7 +732,7 @@ int lenet_pack_fc_x3(ag2_ctx* c, const float* w3p) {
   LeNetDev& d = c->net;
   AG2_HIP(c, d.w3x.reserve(w3x.size() * 2));
   AG2_HIP(c, hipMemcpyAsync(d.w3x.p, w3x.data(), w3x.size() * 2, hipMemcpyHostToDevice, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   return 0;
 }
 

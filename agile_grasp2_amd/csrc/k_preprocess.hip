@@ -1017,7 +1017,7 @@ static int preprocess_resident(ag2_ctx* c, size_t n, bool have_cam, bool have_nr
       if (rc) return rc;
       PreFrame hf;
       AG2_HIP(c, hipMemcpyAsync(pin_small(c), c->d_preframe.p, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
-      AG2_HIP(c, hipStreamSynchronize(c->stream));
+      AG2_HIP(c, ag2::stream_sync(c));
       __builtin_memcpy(&hf, pin_small(c), sizeof(hf));
       if (!(hf.flags & (kPreGridTooLarge | kPreTooManyVoxels))) {
         const size_t m = hf.n_vox;
@@ -1053,7 +1053,7 @@ static int preprocess_resident(ag2_ctx* c, size_t n, bool have_cam, bool have_nr
                      have_nrm ? c->d_tmp.as<float4>() : (float4*)nullptr);
   PreStats hs;
   AG2_HIP(c, hipMemcpyAsync(pin_small(c), ps, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   __builtin_memcpy(&hs, pin_small(c), sizeof(hs));
   const size_t m = hs.n_keep;
   if (!voxelize || m == 0) {
@@ -1112,7 +1112,7 @@ static int preprocess_resident(ag2_ctx* c, size_t n, bool have_cam, bool have_nr
   AG2_HIP(c, hipGetLastError());
   unsigned n_vox = 0;
   AG2_HIP(c, hipMemcpyAsync(pin_small(c), wrank + words, 4, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   __builtin_memcpy(&n_vox, pin_small(c), 4);
   // the voxel lattice spans [mn, (dims - 1) * cell + mn] per axis (both end voxels are occupied, by
   // the extreme points); same float expression as k_vox_emit
@@ -1167,7 +1167,7 @@ int ag2_preprocess_cloud(ag2_ctx* c, const float* xyz, size_t n, size_t stride_b
     AG2_HIP(c, c->d_raw_nrm.reserve(n * 16));
     AG2_HIP(c, hipMemcpyAsync(c->d_raw_nrm.p, nf.data(), n * 16, hipMemcpyHostToDevice, c->stream));
   }
-  AG2_HIP(c, hipStreamSynchronize(c->stream));  // staging vectors go out of scope
+  AG2_HIP(c, ag2::stream_sync(c));  // staging vectors go out of scope
   // without explicit masks every voxel gets the one-camera mask 1 that k_vox_emit writes
   return preprocess_resident(c, n, cam_source != nullptr || n_cams > 1, normals != nullptr && n > 0,
                              filter_workspace, voxelize, voxel_size, flags, n_out);
@@ -1199,7 +1199,7 @@ int ag2_get_cloud(ag2_ctx* c, float* xyz_nx3, int32_t* cam_source, size_t cap, s
   if (c->n == 0) return 0;
   std::vector<float> pack(c->n * 4);
   AG2_HIP(c, hipMemcpyAsync(pack.data(), c->d_xyz_in.p, c->n * 16, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   const int n_cams = c->p.n_cams;
   for (size_t i = 0; i < c->n; i++) {
     if (xyz_nx3) {
@@ -1224,7 +1224,7 @@ int ag2_get_samples(ag2_ctx* c, int32_t* idx, size_t cap, size_t* n) {
   if (c->n_resident_samples && !idx) return set_err(c, AG2_ERR_ARG, "idx is NULL");
   if (c->n_resident_samples) {
     AG2_HIP(c, hipMemcpyAsync(idx, c->d_samples.p, c->n_resident_samples * 4, hipMemcpyDeviceToHost, c->stream));
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
   }
   return 0;
 }
@@ -1265,7 +1265,7 @@ int ag2_subsample_uniformly(ag2_ctx* c, size_t num_samples, uint64_t seed, int32
     PreFrame hf;
     AG2_HIP(c, hipMemcpyAsync(pin_small(c), pf, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
     if (idx_out) AG2_HIP(c, hipMemcpyAsync(idx_out, out, k * 4, hipMemcpyDeviceToHost, c->stream));
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
     __builtin_memcpy(&hf, pin_small(c), sizeof(hf));
     done = hf.flags == 0u;
     if (done) {
@@ -1296,7 +1296,7 @@ int ag2_subsample_uniformly(ag2_ctx* c, size_t num_samples, uint64_t seed, int32
   AG2_HIP(c, hipGetLastError());
   if (idx_out) {
     AG2_HIP(c, hipMemcpyAsync(idx_out, out, k * 4, hipMemcpyDeviceToHost, c->stream));
-    AG2_HIP(c, hipStreamSynchronize(c->stream));
+    AG2_HIP(c, ag2::stream_sync(c));
   }
   c->n_resident_samples = k;
   return 0;

@@ -230,7 +230,7 @@ int compact_slots(ag2_ctx* c, size_t n_slots, int mode, DevBuf& out_list, size_t
   if (rc) return rc;
   unsigned total = 0;
   AG2_HIP(c, hipMemcpyAsync(&total, d_count, 4, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   *n_out = total;
   return 0;
 }
@@ -420,7 +420,7 @@ int gather_records(ag2_ctx* c, const int* d_list, size_t n, std::vector<ag2_hypo
   AG2_HIP(c, hipMemcpyAsync(recs.data(), d_rec, n * sizeof(ag2_hypothesis), hipMemcpyDeviceToHost, c->stream));
   if (offs) AG2_HIP(c, hipMemcpyAsync(offs->data(), d_off, n * 8, hipMemcpyDeviceToHost, c->stream));
   if (keep) AG2_HIP(c, hipMemcpyAsync(keep->data(), d_keep, n, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   return 0;
 }
 
@@ -599,7 +599,7 @@ int merge_selected(ag2_ctx* c, const void* d_gathered, size_t world, size_t cap_
   int rc = pin_reserve(c, bytes);
   if (rc) return rc;
   AG2_HIP(c, hipMemcpyAsync(pin_bulk(c), out, bytes, hipMemcpyDeviceToHost, c->stream));
-  AG2_HIP(c, hipStreamSynchronize(c->stream));
+  AG2_HIP(c, ag2::stream_sync(c));
   unsigned kn[4];
   __builtin_memcpy(kn, pin_bulk(c) + k_cap * sizeof(ag2_hypothesis), 16);
   *n_selected = kn[0];

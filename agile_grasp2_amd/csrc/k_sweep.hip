@@ -1281,7 +1281,7 @@ int upload_samples(ag2_ctx* c, const int32_t* sample_idx, const double* sample_x
   AG2_HIP(c, c->d_sample_q.reserve(std::max<size_t>(s, 1) * 16));
   AG2_HIP(c, c->d_frames.reserve(std::max<size_t>(s, 1) * 12 * 8));
   AG2_HIP(c, c->d_frame_ok.reserve(std::max<size_t>(s, 1) * 4));
-  if (s == 0) return 0;
+  if (s == 0 || c->queries_preset) return 0;  // (preset: the importance sampler wrote d_sample_q)
   // (frame_ok needs no clearing: k_frames writes it for every sample)
   if (sample_idx || !sample_xyz) {
     const int* d_idx = c->d_samples.as<int>();  // left by ag2_subsample_uniformly
@@ -1308,7 +1308,7 @@ int upload_samples(ag2_ctx* c, const int32_t* sample_idx, const double* sample_x
       q[4 * i] = x; q[4 * i + 1] = y; q[4 * i + 2] = z; q[4 * i + 3] = ok ? 1.f : 0.f;
     }
     AG2_HIP(c, hipMemcpyAsync(c->d_sample_q.p, q.data(), s * 16, hipMemcpyHostToDevice, c->stream));
-    AG2_HIP(c, hipStreamSynchronize(c->stream));  // q goes out of scope
+    AG2_HIP(c, ag2::stream_sync(c));  // q goes out of scope
   }
   return 0;
 }

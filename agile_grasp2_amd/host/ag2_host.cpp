@@ -1027,7 +1027,8 @@ std::vector<GraspHypothesis> GraspDetector::detectGraspPoses(const CloudCamera& 
 }
 
 std::vector<GraspHypothesis> GraspDetector::detectImpl(const CloudCamera& cloud_cam, bool clusters_grasps,
-                                                       const Matrix3Xd* samples_xyz, bool cloud_is_resident) {
+                                                       const Matrix3Xd* samples_xyz, bool cloud_is_resident,
+                                                       DeviceImportance* importance) {
   std::vector<GraspHypothesis> out;
   const int hs_inliers = handle_search_.getMinInliers();
   const int min_inliers = (clusters_grasps && hs_inliers > 0) ? hs_inliers : 0;  // :228-236
@@ -1099,6 +1100,29 @@ std::vector<GraspHypothesis> GraspDetector::detectImpl(const CloudCamera& cloud_
           fprintf(stderr, "GraspDetector::detectGraspPoses: %s\n", err_.c_str());
           return out;
         }
+      } else if (!rc && importance && !use_samples && !multi) {
+        // ImportanceSampling on the device: the loop clusters all its hands at the end (importance_sampling.cpp:104-108)
+        rc = ag2_set_min_inliers(c, hs_inliers);
+        const auto top = [&](size_t m) { return p_.num_selected >= 0 ? std::min(m, (size_t)p_.num_selected) : m; };
+        recs.resize(std::max<size_t>(1, top(cap) + (size_t)std::max(importance->prm.num_iterations, 0) *
+                                             top((size_t)std::max(importance->prm.num_samples, 0) *
+                                                 (size_t)p_.num_orientations)));
+        if (!rc) {
+          rc = ag2_detect_importance(c, pidx, s, p_.seed, do_prune ? 1 : 0, &importance->prm, recs.data(), recs.size(), &n);
+          if (rc == AG2_ERR_CAPACITY) {
+            recs.resize(n);
+            rc = ag2_detect_importance(c, pidx, s, p_.seed, do_prune ? 1 : 0, &importance->prm, recs.data(), recs.size(),
+                                       &n);
+          }
+        }
+        size_t nr = 0;
+        if (!rc) rc = ag2_get_importance_rounds(c, nullptr, 0, &nr);  // (the size)
+        if (!rc && nr) {
+          importance->rounds.resize(nr);
+          rc = ag2_get_importance_rounds(c, importance->rounds.data(), nr, &nr);
+        }
+        if (!rc) rc = ag2_get_importance_info(c, &importance->info);
+        importance->ran = rc == 0;
       } else if (!rc) {
         rc = ag2_detect(c, pidx, pxyz, s, 0, p_.seed, do_prune ? 1 : 0, recs.data(), cap, &n, nullptr, 0, nullptr);
       }
@@ -1625,6 +1649,25 @@ double ImportanceSampling::gaussian(uint64_t round, uint64_t* counter) const {
 std::vector<GraspHypothesis> ImportanceSampling::detectGraspPoses(const CloudCamera& cloud_cam_in) {
   const CloudCamera& cloud_cam = cloud_cam_in;
   rounds_.clear();
+  if (sample_on_device_ && params().antipodal_mode == PREDICTION && !getUseIncomingSamples() &&
+      params().devices.size() <= 1) {  // the whole loop in one ag2_detect_importance call
+    DeviceImportance di;
+    ag2_default_importance_params(&di.prm);
+    di.prm.num_iterations = num_iterations_;
+    di.prm.num_samples = num_samples_is_;
+    di.prm.prob_rand_samples = prob_rand_samples_;
+    di.prm.radius = radius_;
+    di.prm.method = sampling_method_;
+    std::vector<GraspHypothesis> hands = detectImpl(cloud_cam, false, nullptr, false, &di);
+    n_initial_ = (int)di.info.n_initial;
+    const size_t per = 3 * (size_t)std::max(num_samples_is_, 0);
+    for (size_t r = 0; per && r < di.rounds.size() / per; r++) {
+      Matrix3Xd m(3, num_samples_is_);
+      std::copy(di.rounds.begin() + (long)(r * per), di.rounds.begin() + (long)((r + 1) * per), m.data());
+      rounds_.push_back(m);
+    }
+    return hands;
+  }
   // 1. initial grasp hypotheses (importance_sampling.cpp:38)
   std::vector<GraspHypothesis> hands = detectImpl(cloud_cam, false, nullptr, false);
   n_initial_ = (int)hands.size();

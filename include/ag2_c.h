@@ -408,6 +408,64 @@ int ag2_find_clusters(ag2_ctx* c, const ag2_hypothesis* hands, size_t n, int min
  * passed min_score_diff before the top num_selected are taken (grasp_detector.cpp:228-236). */
 int ag2_set_min_inliers(ag2_ctx* c, int min_inliers);
 
+/* ---- ImportanceSampling::detectGraspPoses, importance_sampling.cpp:30-118 (use_importance_sampling of the node,
+ * grasp_detection_node.cpp:19,112,135) ----
+ * The initial detect = ag2_detect(sample_idx, s, slot_base 0, seed, do_prune) without clustering; then
+ * num_iterations rounds, each drawing num_samples xyz samples around the hands found so far and running
+ * ag2_detect(sample_xyz = those samples, slot_base 0, seed, do_prune) on them, its selected records appended in
+ * ag2_detect's order; finally, when ag2_set_min_inliers > 0, ag2_find_clusters over all the hands (output in
+ * input order).  No hand from the initial detect: an empty result and no rounds.  Same bytes as that composition.
+ * Round `it`, candidate c takes the counter draws 7c .. 7c+6 of draw(seed, 0xFFFFFFFFFFFF0000 + it, .): a pick
+ * (draw % hands) and three Box-Muller pairs, x = surface + g * radius; MAX accepts x iff its own density is >= the
+ * maximum over all hands, SUM accepts every x; the first num_samples - (int)(prob_rand_samples * num_samples)
+ * accepted candidates are kept (at most 10^6 candidates; slots left unfilled are (0, 0, 0)).  Random sample q reads
+ * counter 7 * tried + (q - num_gauss) and takes that point of the context's cloud (ag2_get_cloud order).  The
+ * sampler runs on the device; log, cos, sqrt and exp are the device's (last-ulp differences from glibc possible).
+ * From the second call with the same s, num_samples, num_iterations and do_prune the whole loop is queued at once
+ * and the host waits ONCE (when MAX can collect at most AG2_IMPORTANCE_MAX_HANDS hands); a call whose shapes did not
+ * hold runs again step by step (ag2_get_importance_info;
+ * AG2_DETECT_STEPWISE=1 in the environment keeps the step-by-step form, for A/B).
+ * *n_out = hands returned; more than cap: AG2_ERR_CAPACITY with *n_out the size needed.  MAX with more than
+ * AG2_IMPORTANCE_MAX_HANDS hands before a round: AG2_ERR_CAPACITY.  Afterwards ag2_get_counters / ag2_get_stage_times
+ * describe the call's last detect. */
+#define AG2_IS_SUM 1
+#define AG2_IS_MAX 2
+#define AG2_IMPORTANCE_MAX_ROUNDS 64
+#define AG2_IMPORTANCE_MAX_HANDS 8192  /* MAX: hands a round may draw around (each candidate evaluates all of them) */
+typedef struct ag2_importance_params {
+  int32_t num_iterations;   /* 5   (at most AG2_IMPORTANCE_MAX_ROUNDS) */
+  int32_t num_samples;      /* 50  per round */
+  double prob_rand_samples; /* 0.3 share of the round's samples drawn uniformly from the cloud */
+  double radius;            /* 0.02 sigma of the Gaussians */
+  int32_t method;           /* AG2_IS_MAX */
+  int32_t reserved;
+} ag2_importance_params;
+typedef struct ag2_importance_info {
+  int64_t host_syncs;   /* waits for the device in the last call, measured: stream / event synchronisations, synchronous
+                           copies and flag polls on the context, and device buffers freed (hipFree waits; counted
+                           process-wide); 1 when it ran in one trip */
+  int64_t one_trip;     /* 1: the last call was served by the queued form */
+  int64_t redone;       /* 1: it was queued, its shapes did not hold, and it ran again step by step */
+  int64_t n_initial;    /* hands of the initial detect */
+  int64_t rounds;       /* rounds run */
+  int64_t num_samples;
+  int64_t n_hands;      /* hands of all rounds, before the clustering */
+  int64_t n_out;        /* hands returned */
+  int64_t tried[AG2_IMPORTANCE_MAX_ROUNDS];     /* candidates drawn per round */
+  int64_t accepted[AG2_IMPORTANCE_MAX_ROUNDS];  /* ... and kept (<= num_gauss) */
+} ag2_importance_info;
+void ag2_default_importance_params(ag2_importance_params* p);
+int ag2_detect_importance(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint64_t seed, int do_prune,
+                          const ag2_importance_params* ip, ag2_hypothesis* out, size_t cap, size_t* n_out);
+/* The sampler alone, one round: `round` (the stream), n_hands surfaces 3 x n_hands, the context's cloud for the
+ * random samples; xyz: 3 x num_samples out; tried / accepted (may be NULL): candidates drawn and kept. */
+int ag2_importance_sample(ag2_ctx* c, const double* surfaces_3xh, size_t n_hands, const ag2_importance_params* ip,
+                          int round, uint64_t seed, double* xyz, int64_t* tried, int64_t* accepted);
+/* The samples of the last call's rounds: rounds x (3 x num_samples) doubles, round-major, column-major within a
+ * round; *n = doubles.  xyz == NULL with cap == 0 only asks for the size; a smaller cap: AG2_ERR_CAPACITY. */
+int ag2_get_importance_rounds(ag2_ctx* c, double* xyz, size_t cap, size_t* n);
+int ag2_get_importance_info(ag2_ctx* c, ag2_importance_info* out);
+
 int ag2_get_counters(ag2_ctx* c, ag2_counters* out);
 int ag2_get_stage_times(ag2_ctx* c, ag2_times* out);
 

@@ -131,8 +131,17 @@ class GraspDetector {
   // detectGraspPoses with the two things ImportanceSampling needs: samples given as xyz regardless
   // of use_incoming_samples_, and "the context already holds this cloud and its normals" (the
   // reference rebuilds the kd-tree and recomputes every normal on each re-entry, hand_search.cpp:11-29)
+  // `importance` (index samples, one device, PREDICTION): the whole importance-sampling loop in one
+  // ag2_detect_importance call in place of the one detect; its rounds and report are left in *importance.
+  struct DeviceImportance {
+    ag2_importance_params prm{};
+    std::vector<double> rounds;  // rounds x (3 x num_samples), as ag2_get_importance_rounds
+    ag2_importance_info info{};
+    bool ran = false;
+  };
   std::vector<GraspHypothesis> detectImpl(const CloudCamera& cloud_cam, bool clusters_grasps,
-                                          const ag2::Matrix3Xd* samples_xyz, bool cloud_is_resident);
+                                          const ag2::Matrix3Xd* samples_xyz, bool cloud_is_resident,
+                                          DeviceImportance* importance = nullptr);
   const Params& params() const { return p_; }
   std::shared_ptr<ag2::Context> context() const { return ctx_; }
 

@@ -36,6 +36,11 @@ class ImportanceSampling : public GraspDetector {
   void setProbRandSamples(double p) { prob_rand_samples_ = p; }
   void setRadius(double r) { radius_ = r; }
   void setSamplingMethod(int m) { sampling_method_ = m; }
+  // true: detectGraspPoses runs the whole loop on the device in one ag2_detect_importance call (same hands as the
+  // host loop up to the last ulp of the device's log / cos / sqrt / exp in the sampler) when the configuration
+  // allows it -- PREDICTION, sample indices, one device; otherwise, and by default, the host loop below.
+  void setSampleOnDevice(bool v) { sample_on_device_ = v; }
+  bool getSampleOnDevice() const { return sample_on_device_; }
   // the xyz samples of every round of the last call (3 x num_samples each), for inspection
   const std::vector<ag2::Matrix3Xd>& lastSampleRounds() const { return rounds_; }
   int lastInitialCount() const { return n_initial_; }
@@ -47,6 +52,7 @@ class ImportanceSampling : public GraspDetector {
   int sampling_method_;
   std::vector<ag2::Matrix3Xd> rounds_;
   int n_initial_ = 0;
+  bool sample_on_device_ = false;
 };
 
 #endif  // AGILE_GRASP2_IMPORTANCE_SAMPLING_H
