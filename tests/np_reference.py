@@ -211,3 +211,91 @@ def lenet_torch(w: dict, images_hwc: np.ndarray) -> np.ndarray:
         x = F.relu(F.linear(x.flatten(1), t["ip1_w"], t["ip1_b"]))
         x = F.linear(x, t["ip2_w"], t["ip2_b"])
     return x.numpy()
+
+
+def _rot3(M, D, k):
+    """(M[0][k] D0 + M[1][k] D1) + M[2][k] D2 over the rows of D: the oracle's association order
+    (BLAS / @ would sum in another order and differ in the last bit)."""
+    return (M[0, k] * D[:, 0] + M[1, k] * D[:, 1]) + M[2, k] * D[:, 2]
+
+
+def antipodal_label(pts, nrm, thresh=0.003):
+    """Antipodal::evaluateGrasp (antipodal.cpp:8-84) on unit-box points / rotated normals (P x 3)."""
+    cos_fc = np.cos(30.0 * np.pi / 180.0)
+    lt, rt = pts[:, 0].min() + thresh, pts[:, 0].max() - thresh
+    lv = (((-1.0 * nrm[:, 0] + 0.0 * nrm[:, 1]) + 0.0 * nrm[:, 2]) > cos_fc) & (pts[:, 0] < lt)
+    rv = (((1.0 * nrm[:, 0] + 0.0 * nrm[:, 1]) + 0.0 * nrm[:, 2]) > cos_fc) & (pts[:, 0] > rt)
+    label = 1 if (lv.any() or rv.any()) else 0
+    if lv.any() and rv.any():
+        ty = min(pts[lv, 1].max(), pts[rv, 1].max())
+        by = max(pts[lv, 1].min(), pts[rv, 1].min())
+        tz = min(pts[lv, 2].max(), pts[rv, 2].max())
+        bz = max(pts[lv, 2].min(), pts[rv, 2].min())
+        if ty > by and tz > bz:
+            label = 2
+    return label
+
+
+def sweep_sample_ordered(D, Q, F, sample, prm, tables):
+    """sweep_sample restated with the oracle's operation order, so that its records are bit-equal
+    to oracle/ag2_oracle.cpp's (sweep_sample) rather than close.
+    D: K2 x 3 float64 centred radius neighbours, widened from float32 (canonical order); Q: their
+    normals; F: 3x3 frame, columns [normal binormal curv]; sample: float64[3];
+    tables: (fs, fsr, cos_t, sin_t, depths) as the oracle derives them.
+    Returns (records, kcrop): each record a dict of the hypothesis fields plus pts / nrm (P x 3)."""
+    fs, fsr, cos_t, sin_t, depths = tables
+    fw, hh = prm["finger_width"], prm["hand_height"]
+    zf = _rot3(F, D, 2)
+    keep = (zf > -1.0 * hh) & (zf < hh)
+    P, Qc = D[keep], Q[keep]
+    out = []
+    if P.shape[0] == 0:
+        return out, 0
+    for oi in range(len(cos_t)):
+        cs, sn = cos_t[oi], sin_t[oi]
+        rot = [[cs, -1.0 * sn, 0.0], [sn, cs, 0.0], [0.0, 0.0, 1.0]]
+        Fr = np.array([[(F[a, 0] * rot[0][b] + F[a, 1] * rot[1][b]) + F[a, 2] * rot[2][b]
+                        for b in range(3)] for a in range(3)])
+        X = np.stack([_rot3(Fr, P, k) for k in range(3)], axis=1)
+        top, bottom = prm["init_bite"], prm["init_bite"] - prm["hand_depth"]
+        below = X[:, 1] < top
+        if not below.any() or (X[below, 1] < bottom).any():
+            continue
+        xb = X[below, 0]
+        free = np.array([not ((xb > fs[k]) & (xb < fsr[k])).any() for k in range(20)])
+        if not free.sum() > 2:
+            continue
+        valid = np.nonzero(free[:10] & free[10:])[0]
+        if len(valid) == 0:
+            continue
+        idx = int(valid[int(np.ceil(len(valid) / 2.0)) - 1])
+        for d in depths:
+            t_, b_ = d, d - prm["hand_depth"]
+            cs_ = X[:, 1] < t_
+            xx = X[cs_, 0]
+            if (X[cs_, 1] < b_).any() or (((xx > fs[idx]) & (xx < fsr[idx])) |
+                                          ((xx > fs[10 + idx]) & (xx < fsr[10 + idx]))).any():
+                break
+            top, bottom = t_, b_
+        left, right = fs[idx] + fw, fs[10 + idx]
+        center = 0.5 * (left + right)
+        surface = X[:, 1].min()
+        box = np.nonzero((X[:, 1] < top) & (X[:, 0] > left) & (X[:, 0] < right))[0]
+        if len(box) == 0:
+            continue
+        rec = dict(orientation=oi, binormal=Fr[:, 0].copy(), approach=Fr[:, 1].copy(),
+                   axis=Fr[:, 2].copy())
+        for name, yv in (("surface", surface), ("bottom", bottom), ("top", top)):
+            rec[name] = np.array([((Fr[a, 0] * center + Fr[a, 1] * yv) + Fr[a, 2] * 0.0) + sample[a]
+                                  for a in range(3)])
+        XB = X[box]
+        nrm = np.stack([_rot3(Fr, Qc[box], k) for k in range(3)], axis=1)
+        rec["width"] = XB[:, 0].max() - XB[:, 0].min()
+        lower = (left - 0.5 * (0.1 - (right - left)), bottom, -1.0 * hh)
+        scales = (1.0 / 0.1, 1.0 / (top - bottom), 1.0 / (2.0 * hh))
+        pts = np.stack([scales[a] * (XB[:, a] - lower[a]) for a in range(3)], axis=1)
+        label = antipodal_label(pts, nrm)
+        rec.update(half_antipodal=int(label >= 1), full_antipodal=int(label == 2),
+                   n_points=len(box), pts=pts, nrm=nrm, hand=idx)
+        out.append(rec)
+    return out, int(P.shape[0])
