@@ -590,9 +590,8 @@ int frame_submit_impl(ag2_ctx* c, const FrameIn& in) {
   if (!in.raw && in.s) p.idx.assign(in.sample_idx, in.sample_idx + in.s);
   f->info.frames++;
   const size_t s_req = in.raw ? in.num_samples : in.s;
-  // Frames the captured sequence cannot take: more than 65536 table slots, an empty frame, the f32-input LeNet
-  // kernels.
-  p.unsupported = s_req * (size_t)R > 65536 || n == 0 || s_req == 0 || !c->net.use_x3;
+  // Frames the captured sequence cannot take: more than 65536 table slots, an empty frame.
+  p.unsupported = s_req * (size_t)R > 65536 || n == 0 || s_req == 0;
   if (f->shapes_known && f->raw != in.raw) {  // the stream changed its entry point: learn the shapes again
     f->shapes_known = false;
     drop_graph(f);

@@ -377,7 +377,7 @@ int ag2_detect_importance(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint6
   const ag2_ctx::IsShapes before = sh;
   const size_t R_or = (size_t)c->p.num_orientations;
   const bool one_trip = !stepwise_only && sh.valid && sh.s == s && sh.num_samples == ip->num_samples &&
-                        sh.rounds == ip->num_iterations && sh.prune == (do_prune ? 1 : 0) && c->net.use_x3 &&
+                        sh.rounds == ip->num_iterations && sh.prune == (do_prune ? 1 : 0) &&
                         !c->fm_on && s > 0 && s * R_or <= 65536 && (size_t)ip->num_samples * R_or <= 65536 &&
                         (ip->method != AG2_IS_MAX || hand_bound(c, sh, *ip) <= (size_t)AG2_IMPORTANCE_MAX_HANDS);
   std::vector<ag2_hypothesis> res;
@@ -396,7 +396,7 @@ int ag2_detect_importance(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint6
   }
   if (sh.cap_img0 != before.cap_img0 || sh.cap_img_r != before.cap_img_r || sh.max_p != before.max_p ||
       sh.s != before.s || sh.num_samples != before.num_samples || sh.rounds != before.rounds || !before.valid) {
-    if (c->net.use_x3 && !c->fm_on && s > 0 && s * R_or <= 65536 && (size_t)ip->num_samples * R_or <= 65536 &&
+    if (!c->fm_on && s > 0 && s * R_or <= 65536 && (size_t)ip->num_samples * R_or <= 65536 &&
         (ip->method != AG2_IS_MAX || hand_bound(c, sh, *ip) <= (size_t)AG2_IMPORTANCE_MAX_HANDS)) {
       rc = is_presize(c, s, *ip);  // (the shapes changed: the next call runs queued at them)
       if (rc) return rc;

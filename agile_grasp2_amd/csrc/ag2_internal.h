@@ -125,10 +125,8 @@ inline size_t cand_capacity(size_t k) {
 
 struct LeNetDev {
   bool loaded = false;
-  DevBuf w1p, b1, w2p, b2, w3p, b3, w4, b4;  // packed for the MFMA lane layout (k_lenet.hip)
-  DevBuf w1x, w2x, w3x;                      // conv / ip1 weights split into 3 bf16 terms (k_lenet_x3.hip)
-  bool use_x3 = true;                        // false: the f32-input MFMA convolutions (AG2_LENET_F32=1)
-  bool use_bands = true;                     // false: k_lenet_conv_x3, one workgroup per image (AG2_LENET_WHOLE=1)
+  DevBuf w1x, w2x, w3x;           // conv / ip1 weights split into 3 bf16 terms, B-fragment order (k_lenet.hip)
+  DevBuf b1, b2, b3, w4, b4;      // biases and ip2, fp32
 };
 
 }  // namespace ag2
@@ -333,7 +331,7 @@ inline hipError_t sync_copy(ag2_ctx* c, void* dst, const void* src, size_t bytes
 }
 
 int set_err(ag2_ctx* c, int code, const std::string& msg);
-enum { kAttrRender = 1u, kAttrLenetConv = 2u, kAttrLenetX3 = 4u, kAttrLenetX3b = 8u };
+enum { kAttrRender = 1u, kAttrLenetX3b = 2u };
 #define AG2_HIP(c, expr)                                                                  \
   do {                                                                                    \
     hipError_t _e = (expr);                                                               \
@@ -448,13 +446,6 @@ int rank_spec_collect(ag2_ctx* c, bool stream_is_idle);  // ag2_pipeline.hip
 int merge_selected(ag2_ctx* c, const void* d_gathered, size_t world, size_t cap_records, ag2_hypothesis* selected,
                    size_t cap, size_t* n_selected, size_t* n_total);
 int make_image_descs(ag2_ctx* c, const int* d_list, size_t n);
-// k_lenet_x3.hip
-int lenet_pack_weights_x3(ag2_ctx* c, const float* conv1_w, const float* conv2_w);
-int launch_lenet_conv_x3(ag2_ctx* c, const uint8_t* d_images, size_t n, float* d_pooled2,
-                         const unsigned* d_n = nullptr);
-int lenet_pack_fc_x3(ag2_ctx* c, const float* w3p_7200x512);
-int launch_lenet_fc1_x3(ag2_ctx* c, size_t n, int* n_pad_out, int* ksplit_out,
-                        const unsigned* d_n = nullptr);
 // ag2_pipeline.hip: frames + sweep + prune compaction of one detect queued without a host wait (statistics stay on
 // the device); sample_idx == NULL with c->queries_preset: the query points are already in d_sample_q
 int enqueue_hypotheses(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint64_t seed, int do_prune);

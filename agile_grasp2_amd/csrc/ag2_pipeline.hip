@@ -497,13 +497,13 @@ int ag2_detect(ag2_ctx* c, const int32_t* sample_idx, const double* sample_xyz, 
   AG2_HIP(c, stage_event(c, 8));
   // The one-round-trip form, when the previous call on this context left its shapes and nothing asks
   // for the step-by-step one (all scored records, the multi-GPU export without read-back,
-  // the f32-input LeNet kernels, AG2_DETECT_STEPWISE=1 for A/B).
+  // AG2_DETECT_STEPWISE=1 for A/B).
   static const bool spec_off = getenv("AG2_DETECT_STEPWISE") != nullptr;
   rc = rank_spec_collect(c, /*stream_is_idle=*/false);  // (a rank's previous call nobody merged or gathered)
   if (rc) return rc;
   // (selected == NULL and cap == 0: a rank of a multi-GPU job -- the caller exports the list and the merge selects)
   const bool rank_mode = !selected && cap == 0 && !(scored_all && cap_all);
-  const bool spec = !spec_off && (selected || rank_mode) && !(scored_all && cap_all) && c->net.use_x3 &&
+  const bool spec = !spec_off && (selected || rank_mode) && !(scored_all && cap_all) &&
                     !c->fm_on && c->spec_cap_img > 0 && c->spec_s == s && c->spec_prune == (do_prune ? 1 : 0) &&
                     n_slots > 0 && n_slots <= 65536;
   if (spec) {

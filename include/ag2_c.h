@@ -109,7 +109,7 @@ typedef struct ag2_times {
   float sweep_ms;       /* K3 k_sweep, first stage (cropped list in LDS), up to the finger-placement gates */
   float compact_ms;     /* prune-flag compaction + image descriptors */
   float render_ms;      /* K4 k_render */
-  float lenet_conv_ms;  /* K5 k_lenet_conv */
+  float lenet_conv_ms;  /* K5 k_lenet_conv_x3b */
   float lenet_fc_ms;    /* K5 k_lenet_fc */
   float select_ms;      /* K6 score scatter, threshold compaction, record gather */
   float total_ms;       /* first to last event of the call */
@@ -196,10 +196,9 @@ int ag2_lenet_load(ag2_ctx* c, const float* conv1_w, const float* conv1_b, const
                    const float* conv2_b, const float* ip1_w, const float* ip1_b,
                    const float* ip2_w, const float* ip2_b);
 /* Classifier::ClassifyBatch / PredictBatch, caffe_classifier.cpp:70-127: n x 2 raw ip2 logits.
- * fp32 like Caffe.  By default conv1, conv2 and ip1 run on the bf16 matrix cores with every fp32
- * operand written as the exact sum of three bf16 terms and fp32 accumulation (deviation from a
- * sequential fp32 evaluation: that of a re-ordered fp32 sum); with AG2_LENET_F32=1 in the
- * environment when ag2_lenet_load is called they run on the f32-input matrix instructions. */
+ * fp32 like Caffe.  conv1, conv2 and ip1 run on the bf16 matrix cores with every fp32 operand
+ * written as the exact sum of three bf16 terms and fp32 accumulation (deviation from a
+ * sequential fp32 evaluation: that of a re-ordered fp32 sum). */
 int ag2_lenet_forward(ag2_ctx* c, const uint8_t* images_hwc, size_t n, float* ip2_out);
 /* GraspDetector::detectGraspPoses, grasp_detector.cpp:84-282 (antipodal_mode PREDICTION, no
  * clustering): hypotheses -> [prune] -> images -> LeNet -> score >= min_score_diff -> top

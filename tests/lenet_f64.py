@@ -20,11 +20,11 @@ output y^ differs from the exact y by
 R is counted per output from the nonzero pattern: summand k counts as nonzero when |x_k| + e_k > 0
 and w_k != 0.  Each nonzero product contributes the largest count of any implementation:
   * conv1, bf16 path: the u8 pixel is one exact bf16 term and products are exact: one summand per
-    nonzero split term of w.  The f32 path, the oracle and torch: one summand and, unless w is a
-    power of two, one product rounding.
+    nonzero split term of w.  The oracle and torch: one summand and, unless w is a power of two, one
+    product rounding.
   * conv2 and ip1, bf16 path: x^ and w are split into (h, m, l); the six products hl, lh, mm, hm, mh, hh
     are kept.  Per product the summands are 3 [w_h != 0] + 2 [w_m != 0] + [w_l != 0] (x^'s own terms
-    are unknown, so all three are assumed present).  This is at least the f32 count of 2.
+    are unknown, so all three are assumed present).  This is at least the fp32 count of 2.
   * ip2 (fmaf chain + shuffle tree on every path): one summand, plus one product rounding unless
     w is a power of two.
 An output with exactly one nonzero summand whose weight is a power of two is exact on every path: the
@@ -67,7 +67,7 @@ def _round16(v: np.ndarray, rne: bool) -> np.ndarray:
 
 
 def split3(v, terms: int = 3, rne: bool = False) -> list[np.ndarray]:
-    """split3 of k_lenet_x3.hip: each term is the running remainder cut to its top 16 bits (a bf16);
+    """split3 of k_lenet.hip: each term is the running remainder cut to its top 16 bits (a bf16);
     terms < 3 or rne=True give the mutant splits."""
     r = np.asarray(v, dtype=np.float32)
     out = []
@@ -430,22 +430,12 @@ def fc1_x3_ksplit(mtiles: int) -> int:
     return 45
 
 
-def fc1_f32_ksplit(mtiles: int) -> int:
-    """The split rule of launch_lenet (k_lenet.hip) for mtiles 64-image tiles (f32 path)."""
-    for s in (1, 3, 5, 15, 25):
-        if mtiles * 4 * s >= 512:
-            return s
-    return 25
-
-
 def split_x3(n: int) -> int:
     return fc1_x3_ksplit((n + 127) // 128)
 
 
-def split_f32(n: int) -> int:
-    return fc1_f32_ksplit((n + 63) // 64)
-
-
-# batch sizes on each side of every change of either rule, up to the first batch that gets split 1
+# batch sizes on each side of every change of the rule, up to the first batch that gets split 1; the
+# pairs 1600 / 1601, 2688 / 2689 and 8128 / 8129 (changes of an earlier rule for 64-image tiles) stay as
+# further sizes
 SPLIT_BATCHES = (1, 512, 513, 896, 897, 1536, 1537, 1600, 1601, 2688, 2689, 2816, 2817, 4736, 4737,
                  8128, 8129, 14208, 14209)

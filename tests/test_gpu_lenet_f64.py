@@ -1,10 +1,9 @@
-"""GPU: every LeNet path against the float64 reference of tests/lenet_f64.py, within its forward-error
+"""GPU: the LeNet kernels against the float64 reference of tests/lenet_f64.py, within its forward-error
 bound -- layer-isolating probes, integer probes (bit for bit), power-of-two scaling (bit for bit), the
 batch sizes at every ip1 split-K change, Xavier networks on realistic images and one detect.
 
-Paths: the default (bf16 three-term split, banded convolutions), AG2_LENET_WHOLE=1 (whole-image
-convolutions) and AG2_LENET_F32=1 (f32-input MFMAs).  The switches are read at weight load.  Each test
-prints max(|err| / bound) per path and input class ("RATIO ..." lines, pytest -s)."""
+PATHS names the one LeNet path (bf16 three-term split, banded convolutions).  Each test prints
+max(|err| / bound) per path and input class ("RATIO ..." lines, pytest -s)."""
 import numpy as np
 import pytest
 
@@ -14,23 +13,19 @@ from agile_grasp2_amd.weights import make_lenet_weights
 
 pytestmark = pytest.mark.gpu
 
-PATHS = {"bands": {}, "whole": {"AG2_LENET_WHOLE": "1"}, "f32": {"AG2_LENET_F32": "1"}}
+PATHS = ("bands",)
 SCALES = (-8, -4, 4, 8)
 
 
-def detector(monkeypatch, path, w, **kw):
+def detector(w, **kw):
     from agile_grasp2_amd import capi
-    for k in ("AG2_LENET_WHOLE", "AG2_LENET_F32"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in PATHS[path].items():
-        monkeypatch.setenv(k, v)
     d = capi.Detector(**kw)
     d.lenet_load(w)
     return d
 
 
-def logits(monkeypatch, path, w, imgs):
-    d = detector(monkeypatch, path, w)
+def logits(w, imgs):
+    d = detector(w)
     try:
         return d.lenet_forward(imgs).astype(np.float64)
     finally:
@@ -50,53 +45,53 @@ def report(cls, ratios):
 
 
 @pytest.mark.parametrize("layer", ["conv1", "conv2", "ip1", "ip2"])
-def test_layer_probes_within_bound(monkeypatch, layer):
+def test_layer_probes_within_bound(layer):
     ratios = dict.fromkeys(PATHS, 0.0)
     for tag, w, imgs in L.layer_probes(layer):
         want = L.forward_f64(w, imgs)
         b = L.bound(w, imgs)
         for path in PATHS:
-            ratios[path] = max(ratios[path], ratio(logits(monkeypatch, path, w, imgs), want, b))
+            ratios[path] = max(ratios[path], ratio(logits(w, imgs), want, b))
     report(f"probe-{layer}", ratios)
     assert max(ratios.values()) <= 1.0, ratios
 
 
 @pytest.mark.parametrize("deep", [False, True])
-def test_integer_probes_bit_exact(monkeypatch, deep):
+def test_integer_probes_bit_exact(deep):
     w, imgs = L.integer_probe(deep=deep)
     want = L.forward_f64(w, imgs)
     for path in PATHS:
-        got = logits(monkeypatch, path, w, imgs)
+        got = logits(w, imgs)
         assert np.array_equal(got, want), (path, np.abs(got - want).max())
 
 
-def test_power_of_two_scaling_bit_exact(monkeypatch):
+def test_power_of_two_scaling_bit_exact():
     for tag, w, imgs in L.realistic_inputs():
         for path in PATHS:
-            base = logits(monkeypatch, path, w, imgs)
+            base = logits(w, imgs)
             for s in SCALES:
-                got = logits(monkeypatch, path, L.scaled(w, s), imgs)
+                got = logits(L.scaled(w, s), imgs)
                 assert np.array_equal(got, np.ldexp(base, 4 * s)), (tag, path, s)
 
 
-@pytest.mark.parametrize("path", list(PATHS))
-def test_split_k_batches_bit_exact(monkeypatch, path):
-    """Both integer probes, their images dealt across batches on each side of every split change of
-    either rule: every split must add up to the float64 logits bit for bit."""
+@pytest.mark.parametrize("path", PATHS)
+def test_split_k_batches_bit_exact(path):
+    """Both integer probes, their images dealt across batches on each side of every split change:
+    every split must add up to the float64 logits bit for bit."""
     probes = [L.integer_probe(seed=3, n_img=64), L.integer_probe(seed=4, n_img=64, deep=True)]
     wants = [L.forward_f64(w, imgs) for w, imgs in probes]
     for (w, imgs), want in zip(probes, wants):
-        d = detector(monkeypatch, path, w)
+        d = detector(w)
         try:
             for n in L.SPLIT_BATCHES:
                 idx = (np.arange(n) * 37 + n) % len(imgs)
                 got = d.lenet_forward(imgs[idx]).astype(np.float64)
-                assert np.array_equal(got, want[idx]), (path, n, L.split_x3(n), L.split_f32(n))
+                assert np.array_equal(got, want[idx]), (path, n, L.split_x3(n))
         finally:
             d.close()
 
 
-def test_realistic_inputs_within_bound(monkeypatch, small_scene):
+def test_realistic_inputs_within_bound(small_scene):
     from agile_grasp2_amd import capi
     xyz, ws, idx = small_scene
     d = capi.Detector(**scene_params(ws))
@@ -111,15 +106,11 @@ def test_realistic_inputs_within_bound(monkeypatch, small_scene):
         cases += [(f"{tag}-zero", w, imgs[:1]), (f"{tag}-255", w, imgs[1:2]),
                   (f"{tag}-dense", w, imgs[2:8]), (f"{tag}-sparse", w, imgs[8:]),
                   (f"{tag}-scene", w, scene_imgs)]
-    worse = []
     for cls, w, imgs in cases:
         want = L.forward_f64(w, imgs)
         b = L.bound(w, imgs)
-        r = report(cls, {path: ratio(logits(monkeypatch, path, w, imgs), want, b) for path in PATHS})
+        r = report(cls, {path: ratio(logits(w, imgs), want, b) for path in PATHS})
         assert max(r.values()) <= 1.0, (cls, r)
-        if r["bands"] > r["f32"]:
-            worse.append(cls)
-    print("RATIO default-worse-than-f32:", worse)
 
 
 def test_detect_scores_within_bound(small_scene):

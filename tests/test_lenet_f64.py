@@ -146,25 +146,23 @@ def test_power_of_two_scaling_is_exact():
                 assert np.array_equal(got, np.ldexp(base[name], 4 * s)), (tag, s, name)
 
 
-def test_split_rules_restate_the_kernels():
+def test_split_rule_restates_the_kernels():
+    """fc1_x3_ksplit above is the rule of ag2_device.h, and the ip1 launch applies it to 128-image tiles."""
     dev = open(os.path.join(ROOT, "agile_grasp2_amd", "csrc", "ag2_device.h")).read()
     assert "const int splits[7] = {1, 3, 5, 9, 15, 25, 45};" in dev
     assert re.search(r"mtiles \* 4 \* splits\[i\] >= 448\) return splits\[i\];\s+return kFc1X3MaxSplit;", dev)
     assert "constexpr int kFc1X3MaxSplit = 45;" in dev
     src = open(os.path.join(ROOT, "agile_grasp2_amd", "csrc", "k_lenet.hip")).read()
-    assert "static const int kSplits[] = {1, 3, 5, 15, 25};" in src
-    assert re.search(r"ksplit = 25;\s+for \(int ks : kSplits\)\s+if \(\(long long\)mtiles \* 4 \* ks >= 512\)", src)
-    assert "mtiles = (int)((n + kFcBM - 1) / kFcBM)" in src and "constexpr int kFcBM = 64;" in src
+    assert "constexpr int kFxBM = 128;" in src and "mtiles = (int)((n + kFxBM - 1) / kFxBM)" in src
+    assert "ksplit = d_n ? kFc1X3MaxSplit : fc1_x3_ksplit(mtiles);" in src
 
 
 def test_split_batches_reach_every_split_on_both_sides_of_every_change():
-    for rule, tile in ((L.split_x3, 128), (L.split_f32, 64)):
-        changes = [n for n in range(2, 20000) if rule(n) != rule(n - 1)]
-        assert rule(changes[-1]) == 1 and all(rule(n) == 1 for n in range(changes[-1], 20000, 97))
-        for n in changes:
-            assert n - 1 in L.SPLIT_BATCHES and n in L.SPLIT_BATCHES, (rule.__name__, n)
-            assert (n - 1) % tile == 0
-        values = {rule(n) for n in L.SPLIT_BATCHES}
-        assert values == {rule(n) for n in range(1, 20000)}, rule.__name__
-    assert [n for n in range(2, 20000) if L.split_x3(n) != L.split_x3(n - 1)] == [513, 897, 1537, 2817, 4737, 14209]
-    assert [n for n in range(2, 20000) if L.split_f32(n) != L.split_f32(n - 1)] == [513, 1601, 2689, 8129]
+    rule = L.split_x3
+    changes = [n for n in range(2, 20000) if rule(n) != rule(n - 1)]
+    assert rule(changes[-1]) == 1 and all(rule(n) == 1 for n in range(changes[-1], 20000, 97))
+    for n in changes:
+        assert n - 1 in L.SPLIT_BATCHES and n in L.SPLIT_BATCHES, n
+        assert (n - 1) % 128 == 0
+    assert {rule(n) for n in L.SPLIT_BATCHES} == {rule(n) for n in range(1, 20000)}
+    assert changes == [513, 897, 1537, 2817, 4737, 14209]
