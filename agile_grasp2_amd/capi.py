@@ -563,6 +563,25 @@ class Detector:
                                                   C.byref(ns), C.byref(nt)))
         return sel[: ns.value].copy(), nt.value
 
+    def gather_begin(self, world: int, cap_records: int):
+        """This context as the root of a one-process gather (ag2_gather_begin): world lists of cap_records records."""
+        self._ck(self.L.ag2_gather_begin(self.h, C.c_size_t(world), C.c_size_t(cap_records)))
+        self._gather = (world, cap_records)
+
+    def gather_selected(self, src: "Detector", rank: int):
+        """src's selected list into position `rank` of this root's gather buffer (ag2_gather_selected)."""
+        src._ck(self.L.ag2_gather_selected(self.h, src.h, C.c_size_t(rank)))
+
+    def merge_gathered(self):
+        """ag2_merge_gathered: as merge_selected_device, on the gather buffer."""
+        world, cap_records = self._gather
+        k = int(self.params.num_selected)
+        cap = world * cap_records if k < 0 else min(k, world * cap_records)
+        sel = np.zeros(max(1, cap), dtype=HYP_DTYPE)
+        ns, nt = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.L.ag2_merge_gathered(self.h, _ptr(sel), C.c_size_t(len(sel)), C.byref(ns), C.byref(nt)))
+        return sel[: ns.value].copy(), nt.value
+
     def set_wait_mode(self, poll: bool = True, spin_us: int = 50):
         """How the host waits for results: poll the flag behind them (spin spin_us, then yield), or the stream."""
         self._ck(self.L.ag2_set_wait_mode(self.h, C.c_int(1 if poll else 0), C.c_int(int(spin_us))))

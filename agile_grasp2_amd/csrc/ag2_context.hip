@@ -119,6 +119,10 @@ int pin_reserve(ag2_ctx* c, size_t bulk_bytes) {
   if (need <= c->h_pin_bytes) return 0;
   // (unconditional: a NULL handle is the HIP default stream, a supported setting -- ag2_set_stream)
   AG2_HIP(c, ag2::stream_sync(c));  // nothing may still be copying
+  {  // (statistics an export of a rank's one-trip detect left in the small area: taken up before it goes)
+    const int rc = rank_spec_collect(c, /*stream_is_idle=*/true);
+    if (rc) return rc;
+  }
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   c->h_pin = nullptr;
   c->h_pin_dev = nullptr;
@@ -282,6 +286,10 @@ int ag2_set_cloud(ag2_ctx* c, const float* xyz, size_t n, size_t stride_bytes,
   if (stride_bytes < 12 || stride_bytes % 4 != 0) return set_err(c, AG2_ERR_ARG, "bad stride");
   if (n > 0 && !xyz) return set_err(c, AG2_ERR_ARG, "xyz is NULL");
   if (n > (size_t)1 << 30) return set_err(c, AG2_ERR_CAPACITY, "more than 2^30 points");
+  {  // (a rank's one-trip detect whose statistics are still in d_stats: taken up before anything rewrites it)
+    const int rcc = rank_spec_collect(c, /*stream_is_idle=*/false);
+    if (rcc) return rcc;
+  }
   c->n = n;
   c->has_cloud = c->has_normals = false;
   c->bounds_known = false;
@@ -329,6 +337,10 @@ int ag2_set_cloud_device(ag2_ctx* c, const void* d_xyz, size_t n, size_t stride_
   if (stride_bytes < 12 || stride_bytes % 4 != 0) return set_err(c, AG2_ERR_ARG, "bad stride");
   if (n > 0 && !d_xyz) return set_err(c, AG2_ERR_ARG, "d_xyz is NULL");
   if (n > (size_t)1 << 30) return set_err(c, AG2_ERR_CAPACITY, "more than 2^30 points");
+  {  // (as ag2_set_cloud)
+    const int rcc = rank_spec_collect(c, /*stream_is_idle=*/false);
+    if (rcc) return rcc;
+  }
   c->n = n;
   c->has_cloud = c->has_normals = false;
   c->bounds_known = false;

@@ -549,6 +549,10 @@ int frame_submit_impl(ag2_ctx* c, const FrameIn& in) {
   if (in.n > (size_t)1 << 30) return set_err(c, AG2_ERR_CAPACITY, "more than 2^30 points");
   if (in.raw && !((float)in.voxel_size > 0.f)) return set_err(c, AG2_ERR_ARG, "voxel_size must be positive");
   if (!c->net.loaded) return set_err(c, AG2_ERR_STATE, "lenet weights not loaded");
+  {  // (a frame rewrites d_stats and d_sel: what a rank's one-trip detect left is taken up first)
+    const int rcr = rank_spec_retire(c);
+    if (rcr) return rcr;
+  }
   if (!c->fm) c->fm = new ag2_frame_state();
   ag2_frame_state* f = c->fm;
   if (f->pend.active) return set_err(c, AG2_ERR_STATE, "a frame is in flight on this context: ag2_wait_frame first");

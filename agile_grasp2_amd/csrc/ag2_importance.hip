@@ -361,7 +361,7 @@ int ag2_detect_importance(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint6
   if (!c->net.loaded) return set_err(c, AG2_ERR_STATE, "lenet weights not loaded");
   if (!sample_idx && s > c->n_resident_samples)
     return set_err(c, AG2_ERR_ARG, "no sample_idx given and fewer than s indices left by ag2_subsample_uniformly");
-  int rc = rank_spec_collect(c, /*stream_is_idle=*/false);
+  int rc = rank_spec_retire(c);
   if (rc) return rc;
   is_reset_info(c, *ip);
   // host waits of this call, measured: every synchronisation the library makes on this context and every hipFree

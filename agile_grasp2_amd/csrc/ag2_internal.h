@@ -220,8 +220,14 @@ struct ag2_ctx {
   // held travels in the header of the exported list (k_export_selected), where EVERY rank sees it after the
   // exchange and takes the same decision (ag2_merge_*: AG2_ERR_RETRY).  The statistics come back in page-locked
   // memory with the export and are taken up at the next point that synchronises anyway (rank_spec_collect).
+  // Any call may come between detect, export and merge: the check stays due until the next detect replaces
+  // d_last_sel, and statistics no export has copied out are read from the device -- before any call rewrites
+  // d_stats (a new cloud, preprocessing, another detect or frame).
   struct RankSpec {
-    bool pending = false;      // a one-trip rank detect whose statistics have not been taken up yet
+    bool check_due = false;       // the last detect ran one trip as a rank: every export of it checks the shapes below
+    bool stats_due = false;       // ... and its statistics have not been taken up yet
+    bool stats_exported = false;  // an export has queued their copy into page-locked memory (kPinRankStats)
+    unsigned status = 0, n_scored = 0;  // once taken up: what the header says (later exports need no d_stats)
     unsigned cap_img = 0;      // images its tail was launched for
     int render_cap = 0;        // in-box points its renderers take
     int stage1_skipped = 0;    // its sweep left the long-list stage out
@@ -443,6 +449,7 @@ int gather_records(ag2_ctx* c, const int* d_list, size_t n, std::vector<ag2_hypo
 int export_candidates_compact(ag2_ctx* c, void* d_dst, size_t cap_records);
 int export_selected_compact(ag2_ctx* c, void* d_dst, size_t cap_records);
 int rank_spec_collect(ag2_ctx* c, bool stream_is_idle);  // ag2_pipeline.hip
+int rank_spec_retire(ag2_ctx* c);  // ag2_pipeline.hip: collect, and no export checks the old detect any more
 int merge_selected(ag2_ctx* c, const void* d_gathered, size_t world, size_t cap_records, ag2_hypothesis* selected,
                    size_t cap, size_t* n_selected, size_t* n_total);
 int make_image_descs(ag2_ctx* c, const int* d_list, size_t n);

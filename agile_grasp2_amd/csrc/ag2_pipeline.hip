@@ -208,7 +208,9 @@ int detect_speculative(ag2_ctx* c, const int32_t* sample_idx, const double* samp
     // held is decided on the device when the list is exported (k_export_selected), read by every rank after the
     // exchange (ag2_merge_*: AG2_ERR_RETRY); the statistics are taken up there as well (rank_spec_collect).
     AG2_HIP(c, stage_event(c, 7));
-    c->rank_spec.pending = true;
+    c->rank_spec.check_due = true;
+    c->rank_spec.stats_due = true;
+    c->rank_spec.stats_exported = false;
     c->rank_spec.cap_img = (unsigned)cap_img;
     c->rank_spec.render_cap = render_capacity_for(c->spec_max_p);
     c->rank_spec.stage1_skipped = c->sweep_stage1_skipped ? 1 : 0;
@@ -286,17 +288,25 @@ void note_detect_stats(ag2_ctx* c, size_t s, const DevStats& hs, size_t n_select
   stage_elapsed(c, &c->times.total_ms, 8, 7);
 }
 
-// Takes up what a rank's one-trip detect left: the statistics k_export_selected copied into page-locked memory
-// (counters, stage times, the shapes the next call is launched at).  Called where the stream has been waited
-// for anyway (merge, gather); elsewhere (stream_is_idle == false) it waits itself.
+// Takes up what a rank's one-trip detect left: its statistics (counters, stage times, the shapes the next call is
+// launched at) -- from page-locked memory when an export has copied them there (k_export_selected), else from the
+// device.  Called where the stream has been waited for anyway (merge, gather, a growing pin_reserve); elsewhere
+// (stream_is_idle == false) it waits itself.
 int rank_spec_collect(ag2_ctx* c, bool stream_is_idle) {
-  if (!c->rank_spec.pending) return 0;
+  if (!c->rank_spec.stats_due) return 0;
   if (!stream_is_idle) AG2_HIP(c, ag2::stream_sync(c));
-  c->rank_spec.pending = false;
   DevStats hs;
-  memcpy(&hs, pin_small(c) + kPinRankStats, sizeof(hs));
+  if (c->rank_spec.stats_exported) {
+    memcpy(&hs, pin_small(c) + kPinRankStats, sizeof(hs));
+  } else {  // (no export yet: d_stats still holds them -- every call that rewrites it takes them up first)
+    AG2_HIP(c, ag2::sync_copy(c, &hs, c->d_stats.p, sizeof(hs), hipMemcpyDeviceToHost));
+  }
+  c->rank_spec.stats_due = false;
+  c->rank_spec.stats_exported = false;
   const bool bad = (hs.err_flags & (1u | 2u | 8u)) != 0u || hs.n_list > c->rank_spec.cap_img ||
                    (int)hs.max_p > c->rank_spec.render_cap || (c->rank_spec.stage1_skipped && hs.n_overflow > 0u);
+  c->rank_spec.status = bad ? 1u : 0u;  // (k_export_selected's decision, from the same statistics)
+  c->rank_spec.n_scored = hs.n_list;
   if (bad) {
     c->spec_fallbacks++;
     c->sweep_no_overflow_runs = 0;
@@ -319,6 +329,14 @@ int rank_spec_collect(ag2_ctx* c, bool stream_is_idle) {
   c->spec_runs++;
   return 0;
 }
+
+// A detect of any kind is about to rewrite d_stats and what d_last_sel points at: take up the statistics of a rank's
+// one-trip detect nobody merged or gathered, and end the check its exports made.
+int rank_spec_retire(ag2_ctx* c) {
+  const int rc = rank_spec_collect(c, /*stream_is_idle=*/false);
+  c->rank_spec.check_due = false;
+  return rc;
+}
 }  // namespace ag2
 
 extern "C" {
@@ -328,6 +346,8 @@ int ag2_local_frames(ag2_ctx* c, const int32_t* sample_idx, const double* sample
   if (!c) return AG2_ERR_ARG;
   (void)hipSetDevice(c->device);
   int rc = check_samples(c, sample_idx, sample_xyz, s);
+  if (rc) return rc;
+  rc = rank_spec_collect(c, /*stream_is_idle=*/false);  // (before d_stats is rewritten)
   if (rc) return rc;
   rc = reset_stats(c);
   if (rc) return rc;
@@ -352,6 +372,8 @@ int ag2_generate_hypotheses(ag2_ctx* c, const int32_t* sample_idx, const double*
   if (!c || !n_out) return AG2_ERR_ARG;
   (void)hipSetDevice(c->device);
   int rc = check_samples(c, sample_idx, sample_xyz, s);
+  if (rc) return rc;
+  rc = rank_spec_collect(c, /*stream_is_idle=*/false);  // (before d_stats is rewritten)
   if (rc) return rc;
   rc = run_hypotheses(c, sample_idx, sample_xyz, s, slot_base, seed, true);
   if (rc) return rc;
@@ -499,7 +521,7 @@ int ag2_detect(ag2_ctx* c, const int32_t* sample_idx, const double* sample_xyz, 
   // for the step-by-step one (all scored records, the multi-GPU export without read-back,
   // AG2_DETECT_STEPWISE=1 for A/B).
   static const bool spec_off = getenv("AG2_DETECT_STEPWISE") != nullptr;
-  rc = rank_spec_collect(c, /*stream_is_idle=*/false);  // (a rank's previous call nobody merged or gathered)
+  rc = rank_spec_retire(c);  // (a rank's previous call nobody merged or gathered)
   if (rc) return rc;
   // (selected == NULL and cap == 0: a rank of a multi-GPU job -- the caller exports the list and the merge selects)
   const bool rank_mode = !selected && cap == 0 && !(scored_all && cap_all);

@@ -967,6 +967,10 @@ static int preprocess_resident(ag2_ctx* c, size_t n, bool have_cam, bool have_nr
   if (voxelize && have_nrm)
     return set_err(c, AG2_ERR_ARG, "normals do not survive voxelisation (cloud_camera.cpp:124-168)");
   if (voxelize && !((float)voxel_size > 0.f)) return set_err(c, AG2_ERR_ARG, "voxel_size must be positive");
+  {  // (a rank's one-trip detect whose statistics are still in d_stats: taken up before anything rewrites it)
+    const int rcc = rank_spec_collect(c, /*stream_is_idle=*/false);
+    if (rcc) return rcc;
+  }
   c->has_cloud = c->has_normals = false;
   AG2_HIP(c, stage_event(c, 14));
   auto finish = [&](size_t m) -> int {

@@ -453,24 +453,25 @@ int export_candidates_compact(ag2_ctx* c, void* d_dst, size_t cap_records) {
 }
 
 // ---- multi-GPU merge: every rank's selected list travels (compact form), every rank ranks them all ----
-// header (16 B): {count, cap, 0, 0}; then min(count, cap) records in list order
-// Header of a rank's list: {count, cap, status, images scored}.  status bit 0: the rank ran its detect at shapes
+// A rank's list: header (16 B) {count, cap, status, images scored}, then min(count, cap) records in list order.
+// status bit 0: the rank ran its detect at shapes
 // learned from its previous call (ag2_ctx::RankSpec) and they did not hold -- more images than the tail was
 // launched for, a longer in-box list than its renderers take, a sweep buffer too small, a sample for the
 // long-list stage that was left out: its list is then void (count 0) and every rank repeats the step.
 struct ExportSpec {
-  const DevStats* st;        // NULL: no statistics to report (header {count, cap, 0, 0})
+  const DevStats* st;        // NULL: status and n_scored below go into the header as they are
   DevStats* st_host;         // page-locked copy of the statistics for the rank's host (or NULL)
   unsigned check;            // 1: the shapes below are to be checked against *st
   unsigned cap_img;
   int render_cap;
   int stage1_skipped;
+  unsigned status, n_scored;  // (the host's decision once it has taken the statistics up: RankSpec)
 };
 __global__ void k_export_selected(const uint4* __restrict__ recs, const unsigned* __restrict__ d_count,
                                   unsigned cap, uint4* __restrict__ dst, ExportSpec es) {
   constexpr unsigned kPer = (unsigned)(sizeof(ag2_hypothesis) / 16);
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned status = 0u, n_scored = 0u;
+  unsigned status = es.status, n_scored = es.n_scored;
   if (es.st) {  // (uniform)
     n_scored = es.st->n_list;
     if (es.check)
@@ -489,9 +490,17 @@ __global__ void k_export_selected(const uint4* __restrict__ recs, const unsigned
 int export_selected_compact(ag2_ctx* c, void* d_dst, size_t cap_records) {
   const size_t threads = std::max<size_t>(cap_records, 1) * (sizeof(ag2_hypothesis) / 16);
   ExportSpec es{};
-  if (c->rank_spec.pending && c->h_pin_dev) {
+  if (c->rank_spec.check_due && !c->rank_spec.stats_due) {
+    // every export of a one-trip rank detect checks, whatever came between: once the host has taken its statistics
+    // up (rank_spec_collect), from the decision it took then -- d_stats may have been rewritten since
+    es.status = c->rank_spec.status;
+    es.n_scored = c->rank_spec.n_scored;
+  } else if (c->rank_spec.check_due) {
     es.st = c->d_stats.as<DevStats>();
-    es.st_host = reinterpret_cast<DevStats*>(pin_small_dev(c) + kPinRankStats);
+    if (!c->rank_spec.stats_exported && c->h_pin_dev) {  // the first export also hands the statistics to the host
+      es.st_host = reinterpret_cast<DevStats*>(pin_small_dev(c) + kPinRankStats);
+      c->rank_spec.stats_exported = true;
+    }
     es.check = 1u;
     es.cap_img = c->rank_spec.cap_img;
     es.render_cap = c->rank_spec.render_cap;

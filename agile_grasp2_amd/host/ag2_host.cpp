@@ -1026,6 +1026,24 @@ std::vector<GraspHypothesis> GraspDetector::detectGraspPoses(const CloudCamera& 
   return detectImpl(cloud_cam, clusters_grasps, nullptr, false);
 }
 
+namespace {
+
+// Spatial tiles order the samples by a coordinate and cut the cloud by the samples' interval: a sample outside the
+// cloud or at a point with a non-finite coordinate has no place in that order or in any tile (its tile-local index
+// would be -1).  Empty when every sample is usable, else why not (sharding.order_samples_by_x raises the same).
+std::string tile_samples_error(const PointCloudRGB& cloud, const int32_t* idx, size_t s) {
+  for (size_t i = 0; i < s; i++) {
+    if (idx[i] < 0 || (size_t)idx[i] >= cloud.points.size())
+      return "spatial tiling: sample index " + std::to_string(idx[i]) + " is outside the cloud";
+    const ag2::PointXYZRGBA& p = cloud.points[(size_t)idx[i]];
+    if (!(std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z)))
+      return "spatial tiling: sample index " + std::to_string(idx[i]) + " is at a non-finite point";
+  }
+  return std::string();
+}
+
+}  // namespace
+
 std::vector<GraspHypothesis> GraspDetector::detectImpl(const CloudCamera& cloud_cam, bool clusters_grasps,
                                                        const Matrix3Xd* samples_xyz, bool cloud_is_resident,
                                                        DeviceImportance* importance) {
@@ -1035,6 +1053,17 @@ std::vector<GraspHypothesis> GraspDetector::detectImpl(const CloudCamera& cloud_
   if (cloud_cam.getCloudOriginal()->size() == 0) {  // grasp_detector.cpp:86-91
     fprintf(stderr, "Point cloud is empty!\n");
     return out;
+  }
+  if (p_.tiling == Params::TILING_SPATIAL && p_.antipodal_mode == PREDICTION && !samples_xyz &&
+      !use_incoming_samples_) {  // (before any context is touched: the one-device and the N-device form alike)
+    const std::vector<int>& si = cloud_cam.getSampleIndices();
+    const std::vector<int32_t> idx(si.begin(), si.end());
+    const std::string e = tile_samples_error(*cloud_cam.getCloudProcessed(), idx.data(), idx.size());
+    if (!e.empty()) {
+      err_ = e;
+      fprintf(stderr, "GraspDetector::detectGraspPoses: %s\n", err_.c_str());
+      return out;
+    }
   }
   const int n_cams = std::max(1, cloud_cam.getCameraSource().rows());
   std::shared_ptr<ag2::Context> ctx = contextFor(n_cams);
@@ -1297,6 +1326,7 @@ std::vector<int32_t> GraspDetector::orderSamplesAlongLongestAxis(const CloudCame
 // Host-only view of the tile plan (no GPU is touched): what TILING_SPATIAL does with a cloud and a sample list --
 // the ordered list, the ranges of equal summed neighbour counts, and per rank the points its tile holds.  Used by the
 // CPU tests to hold this port against agile_grasp2_amd/sharding.py; a site can use it to size its devices.
+// Returns -1 on a bad argument, -2 when a sample is outside the cloud or at a non-finite point (nothing written).
 extern "C" int ag2host_tile_plan(const float* xyz, size_t n, const int32_t* idx, size_t s, int world, double radius_hands,
                                  double halo, int32_t* ordered_out, int64_t* bounds_out, int64_t* tile_points_out,
                                  int32_t* axis_out) {
@@ -1308,6 +1338,7 @@ extern "C" int ag2host_tile_plan(const float* xyz, size_t n, const int32_t* idx,
     cloud->points[i].y = xyz[3 * i + 1];
     cloud->points[i].z = xyz[3 * i + 2];
   }
+  if (!tile_samples_error(*cloud, idx, s).empty()) return -2;
   CloudCamera cc(cloud, (int)n);
   int axis = 0;
   const std::vector<int32_t> ordered = GraspDetector::orderSamplesAlongLongestAxis(cc, std::vector<int32_t>(idx, idx + s), &axis);

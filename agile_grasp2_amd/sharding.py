@@ -88,8 +88,12 @@ def longest_axis(xyz: np.ndarray) -> int:
 
 def order_samples_by_x(xyz: np.ndarray, sample_idx: np.ndarray, axis: int = 0) -> np.ndarray:
     """The sample list in ascending x -- or another `axis` -- (stable): the rank-count-independent
-    order tiles shard."""
+    order tiles shard.  A sample at a point with a non-finite coordinate has no place in that order
+    or in any tile: ValueError (as the C++ host's spatial tiling refuses it)."""
     sample_idx = np.asarray(sample_idx)
+    bad = ~np.isfinite(np.asarray(xyz, dtype=np.float64)[sample_idx, :3]).all(axis=1)
+    if bad.any():
+        raise ValueError(f"spatial tiling: sample index {int(sample_idx[np.argmax(bad)])} is at a non-finite point")
     return sample_idx[np.argsort(np.asarray(xyz)[sample_idx, axis], kind="stable")]
 
 

@@ -310,7 +310,9 @@ int ag2_export_candidates_device(ag2_ctx* c, void* d_dst, size_t bytes);
  * step grasp_detector.cpp:239-252 -- top num_selected by score -- becomes when the samples are sharded):
  * ag2_export_selected_compact_device leaves the scored records of the last ag2_detect with score >=
  * min_score_diff (list order; BEFORE the clustering, also when ag2_set_min_inliers > 0) in d_dst as a
- * 16-byte header {count, cap, 0, 0} + min(count, cap) records; the ranks all-gather these buffers
+ * 16-byte header {count, cap, status, images scored} + min(count, cap) records (status bit 0: the detect ran at
+ * shapes learned from its previous call that did not hold -- count is then 0 and the merge returns AG2_ERR_RETRY;
+ * status and images scored are 0 for a detect that ran step by step); the ranks all-gather these buffers
  * (RCCL) and every rank calls ag2_merge_selected_device on the gathered world x (16 + cap x 176)
  * bytes: the lists concatenated in rank order (= sample order), then -- when ag2_set_min_inliers > 0 --
  * HandleSearch::findClusters over the WHOLE gathered list (handle_search.cpp:4-80 counts inliers over

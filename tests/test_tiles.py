@@ -465,3 +465,16 @@ def test_cpp_tile_plan_equals_sharding_py():
             assert np.array_equal(o, ordered), (case, world)
             assert np.array_equal(b, bounds), (case, world, b, bounds)
             assert list(t) == tiles, (case, world)
+        # a sample at a non-finite point -- NaN, or an infinite coordinate along the tiling axis: both sides refuse
+        # it (its tile-local index would be -1), and the C++ side writes nothing
+        for b, tag in ((bad[0], "nan"), (bad[2], "inf")):
+            if tag == "inf":
+                xyz[b, sharding.longest_axis(xyz)] = -np.inf
+            idx_bad = np.sort(np.append(idx, b)).astype(np.int32)
+            with pytest.raises(ValueError, match="non-finite"):
+                sharding.order_samples_by_x(xyz, idx_bad, sharding.longest_axis(xyz))
+            o = np.full(s + 1, 7, np.int32)
+            b_out = np.full(3, 7, np.int64)
+            rc = lib.ag2host_tile_plan(xyz.ctypes.data, n, idx_bad.ctypes.data, s + 1, 2, 0.1, halo, o.ctypes.data,
+                                       b_out.ctypes.data, None, None)
+            assert rc == -2 and (o == 7).all() and (b_out == 7).all(), (case, tag, rc)
