@@ -368,27 +368,12 @@ int enqueue_frame(ag2_ctx* c, ag2_frame_state* f, int do_prune) {
   if (c->desc_stride == 0) return set_err(c, AG2_ERR_CAPACITY, "frame mode: more than 65536 table slots");
   // -- K4 images, K5 LeNet, K6 score / threshold (at most cap_img images: the kernels clamp the list
   // length they read, the host sees a longer list in the statistics and repeats the frame) -----------
+  // (no stage events: the callers switch them off around the sequence)
   const size_t cap_img = std::min(f->cap_img, n_slots);
-  AG2_HIP(c, c->d_images.reserve(cap_img * 10800));
-  AG2_HIP(c, c->d_logits.reserve(cap_img * 8));
-  const unsigned* d_n = &st->n_list;
-  rc = launch_render(c, c->d_arena.as<double>(), c->d_desc.as<long long>(),
-                     (const int*)(c->d_desc.as<long long>() + c->desc_stride), cap_img,
-                     c->d_images.as<uint8_t>(), f->cap_p, d_n);
+  const ag2_hypothesis* d_res = nullptr;
+  const unsigned* d_nres = nullptr;
+  rc = enqueue_tail(c, cap_img, f->cap_p, &st->n_list, c->desc_stride, /*cluster=*/true, &d_res, &d_nres);
   if (rc) return rc;
-  rc = launch_lenet(c, c->d_images.as<uint8_t>(), cap_img, c->d_logits.as<float>(), -1, d_n);
-  if (rc) return rc;
-  rc = score_and_select_async(c, c->d_list2.as<int>(), cap_img, &st->n_sel, d_n);
-  if (rc) return rc;
-  // -- grasp clusters between the threshold and the top-k (grasp_detector.cpp:228-236), when asked for ----
-  const ag2_hypothesis* d_res = c->d_sel.as<ag2_hypothesis>();
-  const unsigned* d_nres = &st->n_sel;
-  if (c->min_inliers > 0) {
-    rc = cluster_async(c, d_res, cap_img, d_nres, c->min_inliers, &st->n_clu);
-    if (rc) return rc;
-    d_res = c->d_cluster.as<ag2_hypothesis>();
-    d_nres = &st->n_clu;
-  }
   // -- top-k on the device, written straight into the page-locked block ------------------------------
   ag2_hypothesis* d_rec = (ag2_hypothesis*)((char*)c->fm_args_dev + f->off_rec);
   FrameOut* d_fo = (FrameOut*)((char*)c->fm_args_dev + f->off_out);
@@ -496,7 +481,7 @@ void learn_shapes(ag2_ctx* c, ag2_frame_state* f, const FrameIn& in, size_t n_vo
   const size_t want_img = (((size_t)c->n_img * 2 + 512) + 255) / 256 * 256;
   f->cap_p = std::max(f->cap_p, 2 * c->max_p);  // which renderers the sequence launches
   f->cap_img = std::min(std::max(f->cap_img, want_img), c->fm_s_max * (size_t)R);
-  f->k_cap = (c->p.num_selected >= 0) ? std::min<size_t>((size_t)c->p.num_selected, f->cap_img) : f->cap_img;
+  f->k_cap = k_cap_for(c, f->cap_img);
   f->shapes_known = c->fm_s_max * (size_t)R <= 65536;
   // the sweep's long-list stage: left out of the sequence while no frame has queued a sample for it (a frame that
   // does is repeated step by step and the shapes are learned again, with the stage)
@@ -527,7 +512,7 @@ int run_pending_stepwise(ag2_ctx* c, ag2_frame_state* f) {
   const FrameIn in = pending_in(p);
   const size_t s_req = in.raw ? in.num_samples : in.s;
   const size_t cap = std::max<size_t>(1, s_req * (size_t)c->p.num_orientations);
-  p.recs.resize((c->p.num_selected >= 0) ? std::max<size_t>(1, std::min<size_t>(cap, (size_t)c->p.num_selected)) : cap);
+  p.recs.resize(std::max<size_t>(1, k_cap_for(c, cap)));
   f->info.stepwise_runs++;
   size_t n_vox = in.n, s_used = in.s;
   p.n_selected = p.n_scored = 0;
@@ -671,23 +656,16 @@ int frame_wait_impl(ag2_ctx* c, ag2_hypothesis* selected, size_t cap, size_t* n_
       p.active = false;
       return AG2_ERR_HIP;
     }
-    const unsigned flags = fo->st.err_flags;
-    const bool bad = (flags & (1u | 2u | 8u)) != 0 || fo->g.ncells < 0 || fo->topk_overflow != 0 ||
-                     (size_t)fo->st.n_list > std::min(f->cap_img, c->fm_s_max * (size_t)R) ||
-                     (int)fo->st.max_p > render_capacity_for(f->cap_p) || (in.raw && fo->pre.flags != 0u) ||
-                     (c->fm_skip_stage1 && fo->st.n_overflow > 0);
-    if (bad) {
+    const TailShapes shapes = tail_shapes(std::min(f->cap_img, c->fm_s_max * (size_t)R), f->cap_p, c->fm_skip_stage1);
+    const int64_t why = shapes_missed(fo->st, fo->topk_overflow, shapes) | (fo->g.ncells < 0 ? 16 : 0) |
+                        (in.raw ? ((int64_t)fo->pre.flags << 8) : 0);
+    if (why) {
       if (fo->g.ncells == -2) {
         p.active = false;
         return set_err(c, AG2_ERR_ARG, "a point lies below the grid origin given to ag2_set_grid_origin");
       }
       f->info.fallbacks++;
-      f->info.last_fallback = (int64_t)(flags & (1u | 2u | 8u)) | (fo->g.ncells < 0 ? 16 : 0) |
-                              (fo->topk_overflow ? 32 : 0) |
-                              ((size_t)fo->st.n_list > std::min(f->cap_img, c->fm_s_max * (size_t)R) ? 64 : 0) |
-                              ((int)fo->st.max_p > render_capacity_for(f->cap_p) ? 128 : 0) |
-                              ((c->fm_skip_stage1 && fo->st.n_overflow > 0) ? (1ll << 40) : 0) |
-                              (in.raw ? ((int64_t)fo->pre.flags << 8) : 0);
+      f->info.last_fallback = why;
       f->shapes_known = false;  // learn the shapes again from the step-by-step run
       const int rc = run_pending_stepwise(c, f);
       if (rc) {

@@ -25,12 +25,6 @@ namespace {
 
 constexpr int kIsRedo = 1;
 
-size_t shape_for(size_t n_img) { return ((n_img + n_img / 4 + 256 + 255) / 256) * 256; }
-
-size_t k_cap_for(const ag2_ctx* c, size_t cap_img) {
-  return c->p.num_selected >= 0 ? std::min<size_t>((size_t)c->p.num_selected, cap_img) : cap_img;
-}
-
 IsRound round_params(const ag2_importance_params& ip, uint64_t seed, int it) {
   IsRound r{};
   const int num_rand = (int)(ip.prob_rand_samples * ip.num_samples);
@@ -81,21 +75,12 @@ int enqueue_detect(ag2_ctx* c, const int32_t* sample_idx, bool preset, size_t s,
   c->queries_preset = false;
   if (rc) return rc;
   if (c->desc_stride == 0) return kIsRedo;  // (no descriptors from the compaction)
-  DevStats* st = c->d_stats.as<DevStats>();
-  const unsigned* d_n = &st->n_list;
-  AG2_HIP(c, stage_event(c, 3));
-  rc = launch_render(c, c->d_arena.as<double>(), c->d_desc.as<long long>(),
-                     (const int*)(c->d_desc.as<long long>() + c->desc_stride), cap_img, c->d_images.as<uint8_t>(),
-                     max_p, d_n);
+  const ag2_hypothesis* d_res = nullptr;
+  const unsigned* d_nres = nullptr;
+  rc = enqueue_tail(c, cap_img, max_p, &c->d_stats.as<DevStats>()->n_list, c->desc_stride, /*cluster=*/false, &d_res,
+                    &d_nres);
   if (rc) return rc;
-  AG2_HIP(c, stage_event(c, 4));
-  rc = launch_lenet(c, c->d_images.as<uint8_t>(), cap_img, c->d_logits.as<float>(), 5, d_n);
-  if (rc) return rc;
-  AG2_HIP(c, stage_event(c, 6));
-  rc = score_and_select_async(c, c->d_list2.as<int>(), cap_img, &st->n_sel, d_n);
-  if (rc) return rc;
-  rc = launch_topk(c, c->d_sel.as<ag2_hypothesis>(), &st->n_sel, cap_img, k_cap_for(c, cap_img), d_stage, d_fo,
-                   nullptr);
+  rc = launch_topk(c, d_res, d_nres, cap_img, k_cap_for(c, cap_img), d_stage, d_fo, nullptr);
   if (rc) return rc;
   AG2_HIP(c, stage_event(c, 7));
   return 0;
@@ -106,10 +91,9 @@ size_t hand_bound(const ag2_ctx* c, const ag2_ctx::IsShapes& sh, const ag2_impor
   return k_cap_for(c, sh.cap_img0) + (size_t)ip.num_iterations * k_cap_for(c, sh.cap_img_r);
 }
 
+// (the sweeps of these detects always run the long-list stage)
 bool shapes_held(const FrameOut& fo, size_t cap_img, int max_p) {
-  const DevStats& hs = fo.st;
-  return !(hs.err_flags & (1u | 2u | 8u)) && (size_t)hs.n_list <= cap_img &&
-         (int)hs.max_p <= render_capacity_for(max_p) && !fo.topk_overflow;
+  return shapes_missed(fo.st, fo.topk_overflow, tail_shapes(cap_img, max_p, false)) == 0;
 }
 
 int is_one_trip(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint64_t seed, int do_prune,
@@ -198,8 +182,8 @@ int is_one_trip(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint64_t seed, 
     n_img_r = std::max<size_t>(n_img_r, fo[1 + it].st.n_list);
     max_p = std::max(max_p, (int)fo[1 + it].st.max_p);
   }
-  c->is_shapes.cap_img0 = std::max(c->is_shapes.cap_img0, shape_for(fo[0].st.n_list));
-  c->is_shapes.cap_img_r = std::max(c->is_shapes.cap_img_r, shape_for(n_img_r));
+  c->is_shapes.cap_img0 = std::max(c->is_shapes.cap_img0, grown_cap_img(fo[0].st.n_list));
+  c->is_shapes.cap_img_r = std::max(c->is_shapes.cap_img_r, grown_cap_img(n_img_r));
   c->is_shapes.max_p = std::max(c->is_shapes.max_p, max_p);
   // counters and stage times: those of the last detect queued, as ag2_detect leaves them
   const FrameOut& last = fo[(size_t)R];
@@ -261,8 +245,8 @@ int is_stepwise(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint64_t seed, 
   sh.num_samples = S;
   sh.rounds = R;
   sh.prune = do_prune ? 1 : 0;
-  sh.cap_img0 = shape_for(n_img0);
-  sh.cap_img_r = shape_for(n_img_r);
+  sh.cap_img0 = grown_cap_img(n_img0);
+  sh.cap_img_r = grown_cap_img(n_img_r);
   sh.max_p = max_p;
   return 0;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <vector>
@@ -64,6 +65,26 @@ struct DevStats {
   unsigned int pad1;
   unsigned long long sum_k1;         // neighbours visited by k_normals
 };
+
+// err_flags that say a buffer of the sweep was too small (the step-by-step form grows it and repeats the run)
+constexpr unsigned kSweepBufferFlags = 1u | 2u | 8u;
+
+// The shapes a detect tail was launched at, learned from an earlier call: its image capacity, the longest in-box list
+// its renderers take (render_capacity_for) and whether its sweep left the long-list stage out.
+struct TailShapes {
+  unsigned cap_img;
+  int render_cap;
+  int stage1_skipped;
+};
+
+// Why a tail launched at shapes ts did not hold them, from its statistics and its top-k's overflow, in the encoding
+// of ag2_frame_info::last_fallback: the sweep's buffer flags, 32 top-k overflow, 64 more images than cap_img, 128 a
+// longer in-box list than the renderers take, 1 << 40 a sample queued for the long-list stage that was left out.
+// 0: the shapes held.
+__host__ __device__ inline long long shapes_missed(const DevStats& hs, unsigned topk_overflow, const TailShapes& ts) {
+  return (long long)(hs.err_flags & kSweepBufferFlags) | (topk_overflow ? 32 : 0) | (hs.n_list > ts.cap_img ? 64 : 0) |
+         ((int)hs.max_p > ts.render_cap ? 128 : 0) | (ts.stage1_skipped && hs.n_overflow > 0u ? (1ll << 40) : 0);
+}
 
 // float <-> int whose signed order matches the float order (atomicMin/atomicMax on bounds)
 __host__ __device__ __forceinline__ int f2ord(float f) {
@@ -228,9 +249,7 @@ struct ag2_ctx {
     bool stats_due = false;       // ... and its statistics have not been taken up yet
     bool stats_exported = false;  // an export has queued their copy into page-locked memory (kPinRankStats)
     unsigned status = 0, n_scored = 0;  // once taken up: what the header says (later exports need no d_stats)
-    unsigned cap_img = 0;      // images its tail was launched for
-    int render_cap = 0;        // in-box points its renderers take
-    int stage1_skipped = 0;    // its sweep left the long-list stage out
+    ag2::TailShapes shapes{};  // what its tail was launched at
     size_t s = 0;
   } rank_spec;
   int sweep_no_overflow_runs = 0;   // consecutive runs that handed no sample to the long-list stage
@@ -458,6 +477,19 @@ int make_image_descs(ag2_ctx* c, const int* d_list, size_t n);
 int enqueue_hypotheses(ag2_ctx* c, const int32_t* sample_idx, size_t s, uint64_t seed, int do_prune);
 // ... and the counters / stage times such a detect leaves once the stream has been waited for (its statistics hs)
 void note_detect_stats(ag2_ctx* c, size_t s, const DevStats& hs, size_t n_selected);
+// The tail of a detect behind the prune compaction, queued: stage event 3, images, 4, LeNet (5 between its
+// convolutions and its fully connected layers), 6, score and threshold into d_sel (count in d_stats.n_sel).  n_img:
+// the images, or with d_n their capacity (the list length is then read from *d_n on the device); max_p: the longest
+// in-box list the renderers must take; desc_stride: the image counts follow the offsets at d_desc + desc_stride.
+// cluster: the grasp clusters as well, when min_inliers > 0.  *d_res / *d_nres: what the caller selects from.
+int enqueue_tail(ag2_ctx* c, size_t n_img, int max_p, const unsigned* d_n, size_t desc_stride, bool cluster,
+                 const ag2_hypothesis** d_res, const unsigned** d_nres);
+// image capacity of a one-trip tail for a workload that scored n_img images: a quarter more, whole batches of 256
+inline size_t grown_cap_img(size_t n_img) { return ((n_img + n_img / 4 + 256 + 255) / 256) * 256; }
+// records a top-k over at most n records keeps
+inline size_t k_cap_for(const ag2_ctx* c, size_t n) {
+  return c->p.num_selected >= 0 ? std::min<size_t>((size_t)c->p.num_selected, n) : n;
+}
 // k_importance.hip: one round of the importance sampler, one workgroup
 struct IsRound {
   int method;                   // AG2_IS_SUM / AG2_IS_MAX
@@ -477,6 +509,9 @@ int cluster_async(ag2_ctx* c, const ag2_hypothesis* d_in, size_t n_max, const un
 int launch_render(ag2_ctx* c, const double* d_arena, const long long* d_off, const int* d_cnt,
                   size_t n_img, uint8_t* d_out, int max_p, const unsigned* d_n = nullptr);
 int render_capacity_for(int max_p);
+inline TailShapes tail_shapes(size_t cap_img, int max_p, bool stage1_skipped) {
+  return TailShapes{(unsigned)cap_img, render_capacity_for(max_p), stage1_skipped ? 1 : 0};
+}
 // k_lenet.hip
 int lenet_pack_weights(ag2_ctx* c, const float* c1w, const float* c1b, const float* c2w,
                        const float* c2b, const float* f1w, const float* f1b, const float* f2w,

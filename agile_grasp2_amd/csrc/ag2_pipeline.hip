@@ -155,6 +155,14 @@ int run_hypotheses(ag2_ctx* c, const int32_t* sample_idx, const double* sample_x
   return set_err(c, AG2_ERR_CAPACITY, "point-list arena could not be sized");
 }
 
+// a one-trip detect that held its shapes: the next one is launched at shapes that follow the workload (never below
+// what just ran)
+void note_spec_run(ag2_ctx* c, const DevStats& hs) {
+  c->spec_cap_img = std::max(c->spec_cap_img, grown_cap_img(hs.n_list));
+  c->spec_max_p = std::max(c->spec_max_p, (int)hs.max_p);
+  c->spec_runs++;
+}
+
 // ag2_detect with ONE host round trip.  The step-by-step form reads the sweep's statistics in the
 // middle (it needs the number of images to size the renderer's and LeNet's launches) and sorts the
 // selected records on the host.  From the second call of a context on, the tail is launched at shapes
@@ -170,7 +178,7 @@ int detect_speculative(ag2_ctx* c, const int32_t* sample_idx, const double* samp
                        size_t* n_selected, size_t* n_scored, bool rank_mode) {
   const size_t n_slots = s * (size_t)c->p.num_orientations;
   const size_t cap_img = std::min(c->spec_cap_img, n_slots);
-  const size_t k_cap = (c->p.num_selected >= 0) ? std::min<size_t>((size_t)c->p.num_selected, cap_img) : cap_img;
+  const size_t k_cap = k_cap_for(c, cap_img);
   if (!rank_mode && k_cap > cap) return kSpecRedo;  // (the step-by-step form reports the caller's short buffer)
   if (rank_mode && !c->h_pin_dev) return kSpecRedo;
   c->sweep_may_skip_stage1 = true;
@@ -178,28 +186,18 @@ int detect_speculative(ag2_ctx* c, const int32_t* sample_idx, const double* samp
   c->sweep_may_skip_stage1 = false;
   if (rc) return rc;
   if (c->desc_stride == 0) return kSpecRedo;  // (no descriptors from the compaction: more than 64 Ki slots)
-  DevStats* st = c->d_stats.as<DevStats>();
-  const unsigned* d_n = &st->n_list;
-  AG2_HIP(c, c->d_images.reserve(cap_img * 10800));
-  AG2_HIP(c, c->d_logits.reserve(cap_img * 8));
-  AG2_HIP(c, stage_event(c, 3));
-  rc = launch_render(c, c->d_arena.as<double>(), c->d_desc.as<long long>(),
-                     (const int*)(c->d_desc.as<long long>() + c->desc_stride), cap_img,
-                     c->d_images.as<uint8_t>(), c->spec_max_p, d_n);
-  if (rc) return rc;
-  AG2_HIP(c, stage_event(c, 4));
-  rc = launch_lenet(c, c->d_images.as<uint8_t>(), cap_img, c->d_logits.as<float>(), 5, d_n);
-  if (rc) return rc;
-  AG2_HIP(c, stage_event(c, 6));
   // the top-k kernel writes statistics + records where the host reads them (page-locked memory through
   // its device view): no copy operation behind it
-  const size_t out_bytes = sizeof(FrameOut) + k_cap * sizeof(ag2_hypothesis);
-  rc = pin_reserve(c, out_bytes);
+  rc = pin_reserve(c, sizeof(FrameOut) + k_cap * sizeof(ag2_hypothesis));
   if (rc) return rc;
   if (!c->h_pin_dev) return kSpecRedo;
   FrameOut* d_fo = reinterpret_cast<FrameOut*>(pin_bulk_dev(c));
   ag2_hypothesis* d_rec = reinterpret_cast<ag2_hypothesis*>(d_fo + 1);
-  rc = score_and_select_async(c, c->d_list2.as<int>(), cap_img, &st->n_sel, d_n);
+  const TailShapes shapes = tail_shapes(cap_img, c->spec_max_p, c->sweep_stage1_skipped);
+  DevStats* st = c->d_stats.as<DevStats>();
+  const ag2_hypothesis* d_res = nullptr;
+  const unsigned* d_nres = nullptr;
+  rc = enqueue_tail(c, cap_img, c->spec_max_p, &st->n_list, c->desc_stride, !rank_mode, &d_res, &d_nres);
   if (rc) return rc;
   c->d_last_sel = c->d_sel.p;  // for ag2_export_selected_compact_device
   c->d_last_nsel = &st->n_sel;
@@ -211,21 +209,11 @@ int detect_speculative(ag2_ctx* c, const int32_t* sample_idx, const double* samp
     c->rank_spec.check_due = true;
     c->rank_spec.stats_due = true;
     c->rank_spec.stats_exported = false;
-    c->rank_spec.cap_img = (unsigned)cap_img;
-    c->rank_spec.render_cap = render_capacity_for(c->spec_max_p);
-    c->rank_spec.stage1_skipped = c->sweep_stage1_skipped ? 1 : 0;
+    c->rank_spec.shapes = shapes;
     c->rank_spec.s = s;
     *n_selected = 0;
     if (n_scored) *n_scored = 0;  // (not known yet: ag2_get_counters after the merge / gather)
     return 0;
-  }
-  const ag2_hypothesis* d_res = c->d_sel.as<ag2_hypothesis>();
-  const unsigned* d_nres = &st->n_sel;
-  if (c->min_inliers > 0) {  // grasp clusters between the threshold and the top-k (grasp_detector.cpp:228-236)
-    rc = cluster_async(c, d_res, cap_img, d_nres, c->min_inliers, &st->n_clu);
-    if (rc) return rc;
-    d_res = c->d_cluster.as<ag2_hypothesis>();
-    d_nres = &st->n_clu;
   }
   rc = launch_topk(c, d_res, d_nres, cap_img, k_cap, d_rec, d_fo, nullptr);
   if (rc) return rc;
@@ -239,32 +227,15 @@ int detect_speculative(ag2_ctx* c, const int32_t* sample_idx, const double* samp
   }
   FrameOut fo;
   memcpy(&fo, pin_bulk(c), sizeof(FrameOut));
-  const DevStats& hs = fo.st;
-  // did the shapes hold?  (err_flags: a buffer of the sweep was too small; the step-by-step form grows it)
-  if ((hs.err_flags & (1u | 2u | 8u)) || (size_t)hs.n_list > cap_img ||
-      (int)hs.max_p > render_capacity_for(c->spec_max_p) || fo.topk_overflow ||
-      (c->sweep_stage1_skipped && hs.n_overflow > 0)) {  // (samples were queued for the stage that was left out)
+  if (shapes_missed(fo.st, fo.topk_overflow, shapes)) {  // (the step-by-step form grows what was too small)
     c->sweep_no_overflow_runs = 0;
     return kSpecRedo;
   }
-  note_sweep(c, s, hs, 1);
-  const size_t n_img = hs.n_list;
-  c->cnt.n_pruned = (int64_t)n_img;
-  c->cnt.n_scored = (int64_t)n_img;
-  c->cnt.n_selected = (int64_t)fo.n_out;
+  note_detect_stats(c, s, fo.st, fo.n_out);
+  note_spec_run(c, fo.st);
   *n_selected = fo.n_out;
-  if (n_scored) *n_scored = n_img;
-  stage_elapsed(c, &c->times.compact_ms, 11, 3);
-  stage_elapsed(c, &c->times.render_ms, 3, 4);
-  stage_elapsed(c, &c->times.lenet_conv_ms, 4, 5);
-  stage_elapsed(c, &c->times.lenet_fc_ms, 5, 6);
-  stage_elapsed(c, &c->times.select_ms, 6, 7);
-  stage_elapsed(c, &c->times.total_ms, 8, 7);
+  if (n_scored) *n_scored = fo.st.n_list;
   if (fo.n_out) memcpy(selected, pin_bulk(c) + sizeof(FrameOut), (size_t)fo.n_out * sizeof(ag2_hypothesis));
-  // the shapes follow the workload (never below what just ran)
-  c->spec_cap_img = std::max(c->spec_cap_img, ((n_img + n_img / 4 + 256 + 255) / 256) * 256);
-  c->spec_max_p = std::max(c->spec_max_p, (int)hs.max_p);
-  c->spec_runs++;
   return 0;
 }
 
@@ -288,6 +259,34 @@ void note_detect_stats(ag2_ctx* c, size_t s, const DevStats& hs, size_t n_select
   stage_elapsed(c, &c->times.total_ms, 8, 7);
 }
 
+int enqueue_tail(ag2_ctx* c, size_t n_img, int max_p, const unsigned* d_n, size_t desc_stride, bool cluster,
+                 const ag2_hypothesis** d_res, const unsigned** d_nres) {
+  DevStats* st = c->d_stats.as<DevStats>();
+  const long long* d_off = c->d_desc.as<long long>();
+  AG2_HIP(c, c->d_images.reserve(std::max<size_t>(n_img, 1) * 10800));
+  AG2_HIP(c, c->d_logits.reserve(std::max<size_t>(n_img, 1) * 8));
+  AG2_HIP(c, stage_event(c, 3));
+  int rc = launch_render(c, c->d_arena.as<double>(), d_off, (const int*)(d_off + desc_stride), n_img,
+                         c->d_images.as<uint8_t>(), max_p, d_n);
+  if (rc) return rc;
+  AG2_HIP(c, stage_event(c, 4));
+  rc = launch_lenet(c, c->d_images.as<uint8_t>(), n_img, c->d_logits.as<float>(), 5, d_n);
+  if (rc) return rc;
+  AG2_HIP(c, stage_event(c, 6));
+  // score = ip2[1] - ip2[0], keep score >= min_score_diff, gather in list order
+  rc = score_and_select_async(c, c->d_list2.as<int>(), n_img, &st->n_sel, d_n);
+  if (rc) return rc;
+  *d_res = c->d_sel.as<ag2_hypothesis>();
+  *d_nres = &st->n_sel;
+  if (cluster && c->min_inliers > 0) {  // grasp clusters between the threshold and the top-k (grasp_detector.cpp:228-236)
+    rc = cluster_async(c, *d_res, n_img, *d_nres, c->min_inliers, &st->n_clu);
+    if (rc) return rc;
+    *d_res = c->d_cluster.as<ag2_hypothesis>();
+    *d_nres = &st->n_clu;
+  }
+  return 0;
+}
+
 // Takes up what a rank's one-trip detect left: its statistics (counters, stage times, the shapes the next call is
 // launched at) -- from page-locked memory when an export has copied them there (k_export_selected), else from the
 // device.  Called where the stream has been waited for anyway (merge, gather, a growing pin_reserve); elsewhere
@@ -303,9 +302,8 @@ int rank_spec_collect(ag2_ctx* c, bool stream_is_idle) {
   }
   c->rank_spec.stats_due = false;
   c->rank_spec.stats_exported = false;
-  const bool bad = (hs.err_flags & (1u | 2u | 8u)) != 0u || hs.n_list > c->rank_spec.cap_img ||
-                   (int)hs.max_p > c->rank_spec.render_cap || (c->rank_spec.stage1_skipped && hs.n_overflow > 0u);
-  c->rank_spec.status = bad ? 1u : 0u;  // (k_export_selected's decision, from the same statistics)
+  const bool bad = shapes_missed(hs, 0u, c->rank_spec.shapes) != 0;  // (what k_export_selected decides from them)
+  c->rank_spec.status = bad ? 1u : 0u;
   c->rank_spec.n_scored = hs.n_list;
   if (bad) {
     c->spec_fallbacks++;
@@ -313,20 +311,8 @@ int rank_spec_collect(ag2_ctx* c, bool stream_is_idle) {
     c->spec_cap_img = 0;  // the next call runs step by step and learns the shapes again
     return 0;
   }
-  note_sweep(c, c->rank_spec.s, hs, 1);
-  const size_t n_img = hs.n_list;
-  c->cnt.n_pruned = (int64_t)n_img;
-  c->cnt.n_scored = (int64_t)n_img;
-  c->cnt.n_selected = 0;
-  stage_elapsed(c, &c->times.compact_ms, 11, 3);
-  stage_elapsed(c, &c->times.render_ms, 3, 4);
-  stage_elapsed(c, &c->times.lenet_conv_ms, 4, 5);
-  stage_elapsed(c, &c->times.lenet_fc_ms, 5, 6);
-  stage_elapsed(c, &c->times.select_ms, 6, 7);
-  stage_elapsed(c, &c->times.total_ms, 8, 7);
-  c->spec_cap_img = std::max(c->spec_cap_img, ((n_img + n_img / 4 + 256 + 255) / 256) * 256);
-  c->spec_max_p = std::max(c->spec_max_p, (int)hs.max_p);
-  c->spec_runs++;
+  note_detect_stats(c, c->rank_spec.s, hs, 0);
+  note_spec_run(c, hs);
   return 0;
 }
 
@@ -541,49 +527,28 @@ int ag2_detect(ag2_ctx* c, const int32_t* sample_idx, const double* sample_xyz, 
   if (rc) return rc;
   const size_t n_img = c->n_img;
   // shapes for the next call's one-round-trip form
-  c->spec_cap_img = ((n_img + n_img / 4 + 256 + 255) / 256) * 256;
+  c->spec_cap_img = grown_cap_img(n_img);
   c->spec_max_p = c->max_p;
   c->spec_s = s;
   c->spec_prune = do_prune ? 1 : 0;
   c->cnt.n_pruned = (int64_t)n_img;
-  AG2_HIP(c, c->d_images.reserve(std::max<size_t>(n_img, 1) * 10800));
-  AG2_HIP(c, c->d_logits.reserve(std::max<size_t>(n_img, 1) * 8));
   size_t desc_stride = c->desc_stride;  // the compaction usually wrote the descriptors already
   if (desc_stride == 0) {
-    rc = make_image_descs(c, c->d_list2.as<int>(), n_img);                     // 3a. images
+    rc = make_image_descs(c, c->d_list2.as<int>(), n_img);
     if (rc) return rc;
     desc_stride = n_img;
   }
-  AG2_HIP(c, stage_event(c, 3));
-  rc = launch_render(c, c->d_arena.as<double>(), c->d_desc.as<long long>(),
-                     (const int*)(c->d_desc.as<long long>() + desc_stride), n_img,
-                     c->d_images.as<uint8_t>(), c->max_p);
-  if (rc) return rc;
-  AG2_HIP(c, stage_event(c, 4));
-  rc = launch_lenet(c, c->d_images.as<uint8_t>(), n_img, c->d_logits.as<float>(), 5);  // 3b.
-  if (rc) return rc;
-  AG2_HIP(c, stage_event(c, 6));
-  // 4. score = ip2[1] - ip2[0], keep score >= min_score_diff, gather in order -- all on the device;
-  // one read-back brings the count and (for the usual small lists) the records themselves
-  unsigned* d_nsel = &c->d_stats.as<DevStats>()->n_sel;
-  rc = score_and_select_async(c, c->d_list2.as<int>(), n_img, d_nsel);
-  if (rc) return rc;
-  // 4b. grasp clusters (grasp_detector.cpp:228-236), only when HandleSearch::setMinInliers > 0
-  const void* d_res = c->d_sel.p;
-  const unsigned* d_nres = d_nsel;
-  // What ag2_export_selected_compact_device puts on the wire is the list BEFORE the clustering: clusters
-  // count inliers over the hands of all ranks, so a multi-GPU job clusters in the merge
-  // (ag2_merge_selected_device), on the gathered list -- and a rank that only feeds the merge skips its own.
-  c->d_last_sel = c->d_sel.p;
-  c->d_last_nsel = d_nsel;
+  // 3. images, LeNet, 4. score and threshold -- all on the device; one read-back brings the count and (for the
+  // usual small lists) the records themselves.  What ag2_export_selected_compact_device puts on the wire is the list
+  // BEFORE the clustering: clusters count inliers over the hands of all ranks, so a multi-GPU job clusters in the
+  // merge (ag2_merge_selected_device), on the gathered list -- and a rank that only feeds the merge skips its own.
   const bool merge_follows = !selected && cap == 0 && !(scored_all && cap_all);
-  if (c->min_inliers > 0 && !merge_follows) {
-    unsigned* d_nclu = &c->d_stats.as<DevStats>()->n_clu;
-    rc = cluster_async(c, c->d_sel.as<ag2_hypothesis>(), n_img, d_nsel, c->min_inliers, d_nclu);
-    if (rc) return rc;
-    d_res = c->d_cluster.p;
-    d_nres = d_nclu;
-  }
+  const ag2_hypothesis* d_res = nullptr;
+  const unsigned* d_nres = nullptr;
+  rc = enqueue_tail(c, n_img, c->max_p, nullptr, desc_stride, !merge_follows, &d_res, &d_nres);
+  if (rc) return rc;
+  c->d_last_sel = c->d_sel.p;
+  c->d_last_nsel = &c->d_stats.as<DevStats>()->n_sel;
   AG2_HIP(c, stage_event(c, 7));
   if (merge_follows) {
     // Multi-GPU use: the caller exports the selected list (ag2_export_selected_compact_device) and the
@@ -624,8 +589,7 @@ int ag2_detect(ag2_ctx* c, const int32_t* sample_idx, const double* sample_xyz, 
   // 5. top num_selected by score, descending (grasp_detector.cpp:239-252); ties by position.  Only
   // the order of the first k is needed: indices are (partially) sorted, the 176-byte records are
   // copied once.
-  size_t k = n_anti;
-  if (c->p.num_selected >= 0 && k > (size_t)c->p.num_selected) k = (size_t)c->p.num_selected;
+  const size_t k = k_cap_for(c, n_anti);
   std::vector<uint32_t> order(n_anti);
   for (uint32_t i = 0; i < n_anti; i++) order[i] = i;
   const auto better = [recs](uint32_t a, uint32_t b) {

@@ -462,9 +462,7 @@ struct ExportSpec {
   const DevStats* st;        // NULL: status and n_scored below go into the header as they are
   DevStats* st_host;         // page-locked copy of the statistics for the rank's host (or NULL)
   unsigned check;            // 1: the shapes below are to be checked against *st
-  unsigned cap_img;
-  int render_cap;
-  int stage1_skipped;
+  TailShapes shapes;
   unsigned status, n_scored;  // (the host's decision once it has taken the statistics up: RankSpec)
 };
 __global__ void k_export_selected(const uint4* __restrict__ recs, const unsigned* __restrict__ d_count,
@@ -474,9 +472,7 @@ __global__ void k_export_selected(const uint4* __restrict__ recs, const unsigned
   unsigned status = es.status, n_scored = es.n_scored;
   if (es.st) {  // (uniform)
     n_scored = es.st->n_list;
-    if (es.check)
-      status = ((es.st->err_flags & (1u | 2u | 8u)) != 0u || n_scored > es.cap_img || (int)es.st->max_p > es.render_cap ||
-                (es.stage1_skipped && es.st->n_overflow > 0u)) ? 1u : 0u;
+    if (es.check) status = shapes_missed(*es.st, 0u, es.shapes) ? 1u : 0u;
   }
   const unsigned count = status ? 0u : *d_count;
   const unsigned n = count < cap ? count : cap;
@@ -502,9 +498,7 @@ int export_selected_compact(ag2_ctx* c, void* d_dst, size_t cap_records) {
       c->rank_spec.stats_exported = true;
     }
     es.check = 1u;
-    es.cap_img = c->rank_spec.cap_img;
-    es.render_cap = c->rank_spec.render_cap;
-    es.stage1_skipped = c->rank_spec.stage1_skipped;
+    es.shapes = c->rank_spec.shapes;
   }
   hipLaunchKernelGGL(k_export_selected, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream,
                      (const uint4*)c->d_last_sel, c->d_last_nsel, (unsigned)cap_records, (uint4*)d_dst, es);
@@ -581,7 +575,7 @@ __global__ void __launch_bounds__(256) k_merge_topk(const ag2_hypothesis* __rest
 int merge_selected(ag2_ctx* c, const void* d_gathered, size_t world, size_t cap_records, ag2_hypothesis* selected,
                    size_t cap, size_t* n_selected, size_t* n_total) {
   const size_t n_max = world * cap_records;
-  const size_t k_cap = (c->p.num_selected >= 0) ? std::min<size_t>((size_t)c->p.num_selected, n_max) : n_max;
+  const size_t k_cap = k_cap_for(c, n_max);
   AG2_HIP(c, c->d_merge.reserve((n_max + k_cap + 1) * sizeof(ag2_hypothesis) + 64));
   ag2_hypothesis* flat = c->d_merge.as<ag2_hypothesis>();
   ag2_hypothesis* out = flat + n_max;

@@ -128,6 +128,7 @@ def test_a_frame_that_needs_the_long_list_stage_after_frames_that_did_not():
     assert ds.counters().n_overflow_samples > 0
     fi = df.frame_info()
     assert fi.fallbacks == before + 1 and fi.graph_replays >= 2
+    assert fi.last_fallback & (1 << 40), hex(fi.last_fallback)  # (ag2_frame_info::last_fallback: the long-list stage)
     df.close()
     ds.close()
 
