@@ -61,30 +61,129 @@ def pca_normal(nb_xyz: np.ndarray, p: np.ndarray) -> np.ndarray:
     return n, w
 
 
+def majority_camera(cam_source_cols: np.ndarray) -> int:
+    """HandSearch::calculateLocalFrames' camera vote (hand_search.cpp:133-146): per camera, count the
+    drawn neighbours whose camera_source entry is exactly 1 (:139; a 2 marks "not seen",
+    cloud_camera.cpp:151, and does not count); VectorXi::maxCoeff(&i) returns the FIRST maximum, so
+    a tie goes to the lower camera index.  cam_source_cols: n_cams x m, one column per draw."""
+    votes = (np.asarray(cam_source_cols) == 1).sum(axis=1)
+    return int(np.argmax(votes))  # argmax: first maximum
+
+
 def local_frame(normals_nb: np.ndarray, sample: np.ndarray, cam_origin: np.ndarray,
-                seed: int, slot: int):
+                seed: int, slot: int, cam_source_nb: np.ndarray | None = None, jmax: int | None = None,
+                info: dict | None = None):
     """LocalFrame::findAverageNormalAxis (local_frame.cpp:26-59) on the drawn normals.
-    normals_nb: K x 3 finite neighbour normals in canonical order."""
+    normals_nb: K x 3 finite neighbour normals in canonical order.
+
+    cam_origin: one origin (3,), or with cam_source_nb (n_cams x K, the neighbours' camera_source
+    columns) the origins of every camera (n_cams x 3): the frame then faces the majority camera of
+    the draws (hand_search.cpp:133-146, local_frame.cpp:51-55).  jmax overrides the argmax of
+    :42 (for callers that resolve a near-tie of the column sums); info, if given, receives the
+    draws, the majority camera, the column sums and the eigenvalues of M."""
     k = normals_nb.shape[0]
     m = min(50, k)
     picks = [draw_u64(seed, slot, j) % k for j in range(m)]
+    origin = np.asarray(cam_origin, dtype=np.float64)
+    majority = 0
+    if cam_source_nb is not None:
+        drawn = np.asarray(cam_source_nb)[:, picks]
+        majority = majority_camera(drawn)
+        origin = origin.reshape(-1, 3)[majority]
+        if info is not None:
+            info["votes"] = (drawn == 1).sum(axis=1)
     N = normals_nb[picks].astype(np.float64)
     N = N / np.linalg.norm(N, axis=1, keepdims=True)
     M = N.T @ N
     w, v = np.linalg.eigh(M)
     c = v[:, 0]
     G = (N @ N.T) ** 6
-    jmax = int(np.argmax(G.sum(axis=0)))
+    gsum = G.sum(axis=0)
+    if jmax is None:
+        jmax = int(np.argmax(gsum))
     npart = (np.eye(3) - np.outer(c, c)) @ N[jmax]
     normal = npart / np.linalg.norm(npart)
     binormal = np.cross(c, normal)
-    v2 = sample.astype(np.float64) - cam_origin
+    v2 = sample.astype(np.float64) - origin
     if normal @ v2 > 0:
         normal = -normal
     if binormal @ v2 > 0:
         binormal = -binormal
     curv = np.cross(normal, binormal)
+    if info is not None:
+        info.update(picks=picks, majority=majority, origin=origin, gsum=gsum, jmax=jmax, m=m)
     return normal, binormal, curv, w
+
+
+def hand_constants(prm):
+    """(fs, fsr, cos_t, sin_t, depths) of the hand sweep, derived from the reference in its own
+    operation order:
+      fs      FingerHand ctor, finger_hand.cpp:9-12: fs_half = VectorXd::LinSpaced(10, 0.0, od - fw),
+              finger_spacing_ << (fs_half - od + fw), fs_half.  LinSpaced as Eigen 3.2 (ROS Indigo)
+              evaluates it: low + i * ((high - low) / (n - 1)) for every i (Eigen >= 3.3 returns `high`
+              itself for the last entry: fs[9], fs[19] could then differ by one ulp).
+      fsr     the slot's right edge, finger_spacing_(i) + finger_width_ (finger_hand.cpp:61).
+      angles  hand_search.cpp:179-180: LinSpaced(R + 1, -pi/2, pi/2), first R entries; rot's
+              cos / sin (:357) by libm.
+      depths  FingerHand::deepenHand, finger_hand.cpp:118-122: depth = min_depth + 0.005, then
+              += 0.005 while depth <= max_depth, accumulated in double (min_depth = init_bite,
+              max_depth = hand_depth: hand_search.cpp:373)."""
+    import math
+    od, fw, R = float(prm["hand_outer_diameter"]), float(prm["finger_width"]), int(prm["num_orientations"])
+    n = 10
+    low, high = 0.0, od - fw
+    step = (high - low) / float(n - 1)
+    fs_half = [low + float(i) * step for i in range(n)]
+    fs = np.array([(h - od) + fw for h in fs_half] + fs_half)
+    fsr = np.array([f + fw for f in fs])
+    alow, ahigh = -1.0 * math.pi / 2.0, math.pi / 2.0
+    astep = (ahigh - alow) / float(R)
+    ang = [alow + float(i) * astep for i in range(R)]
+    cos_t = np.array([math.cos(a) for a in ang])
+    sin_t = np.array([math.sin(a) for a in ang])
+    depths = []
+    d = float(prm["init_bite"]) + 0.005
+    while d <= float(prm["hand_depth"]):
+        depths.append(d)
+        d += 0.005
+    return fs, fsr, cos_t, sin_t, np.array(depths)
+
+
+def cloud_min_z(xyz: np.ndarray) -> np.float32:
+    """pcl::getMinMax3D's min_bound(2) over the processed cloud (grasp_detector.cpp:152-153): the float
+    minimum z of the finite points."""
+    xyz = np.asarray(xyz, dtype=np.float32)
+    ok = np.isfinite(xyz[:, :3]).all(axis=1)
+    return np.float32(xyz[ok, 2].min()) if ok.any() else np.float32(np.inf)
+
+
+def prune_corners(rec, prm):
+    """The five points of GraspDetector::pruneGraspsOnHandParameters (grasp_detector.cpp:372-380), in
+    float64: left / right bottom, left / right top (bottom or top +- half_width * binormal), and
+    bottom - 0.10 * approach.  Returns 5 x 3."""
+    hw = 0.5 * float(prm["hand_outer_diameter"])
+    b, t = np.asarray(rec["bottom"], dtype=np.float64), np.asarray(rec["top"], dtype=np.float64)
+    bn, ap = np.asarray(rec["binormal"], dtype=np.float64), np.asarray(rec["approach"], dtype=np.float64)
+    return np.stack([b + hw * bn, b - hw * bn, t + hw * bn, t - hw * bn, b - 0.10 * ap])
+
+
+def prune_keep(rec, prm, min_z) -> bool:
+    """GraspDetector::pruneGraspsOnHandParameters (grasp_detector.cpp:363-395) for one record.
+    :369 a record that is not half antipodal is dropped when filter_half_grasps is set; :383-387 the
+    aperture bounds are inclusive (>= min_aperture, <= max_aperture, doubles); the workspace bounds
+    and min_z are `float` parameters (:363-364: the double workspace_ narrows at the call, :154), the
+    corner coordinates stay double and are compared against the widened floats, inclusively.
+    min_z: cloud_min_z of the processed cloud (:152-154)."""
+    if int(prm.get("filter_half_grasps", 0)) and not int(rec["half_antipodal"]):
+        return False
+    ws = prm["workspace"]
+    min_x, max_x, min_y, max_y = (float(np.float32(ws[i])) for i in range(4))
+    P = prune_corners(rec, prm)
+    ap = float(rec["width"])
+    return bool(ap >= float(prm["min_aperture"]) and ap <= float(prm["max_aperture"])
+                and P[:, 2].min() >= float(np.float32(min_z))
+                and P[:, 1].min() >= min_y and P[:, 1].max() <= max_y
+                and P[:, 0].min() >= min_x and P[:, 0].max() <= max_x)
 
 
 def finger_tables(od=0.09, fw=0.01):
@@ -187,12 +286,12 @@ def render_image(U: np.ndarray, Y: np.ndarray) -> np.ndarray:
     np.add.at(acc, cell[ok], Y[ok])  # sequential, in order
     cnt = np.bincount(cell[ok], minlength=S * S)
     img = np.zeros((S, S, 3), dtype=np.float32)
-    for c in np.nonzero(cnt)[0]:
-        a = acc[c]
-        with np.errstate(all="ignore"):
-            v = np.abs((1.0 / np.sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2])) * a)
-        v = np.where(np.isnan(v), 0.0, v)
-        img[S - 1 - c // S, c % S] = v.astype(np.float32)
+    c = np.nonzero(cnt)[0]
+    a = acc[c]
+    with np.errstate(all="ignore"):  # per cell, elementwise: the same operations as a loop over cells
+        v = np.abs((1.0 / np.sqrt((a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2]))[:, None] * a)
+    v = np.where(np.isnan(v), 0.0, v)
+    img[S - 1 - c // S, c % S] = v.astype(np.float32)
     dil = maximum_filter(img, size=(3, 3, 1), mode="constant", cval=0.0)
     rgb = dil[:, :, ::-1]
     t = rgb.astype(np.float32) * np.float32(255.0)
