@@ -32,6 +32,7 @@ SYMBOLS = [
     "ag2_pipe_wait", "ag2_set_wait_mode", "ag2_get_wait_info",
     "ag2_default_importance_params", "ag2_detect_importance", "ag2_get_importance_rounds", "ag2_get_importance_info",
     "ag2_importance_sample",
+    "ag2_set_cloud_desc", "ag2_detect_frame_desc", "ag2_submit_frame_desc", "ag2_pipe_submit_desc",
 ]
 
 
@@ -73,6 +74,47 @@ class FrameInfo(C.Structure):
 class WaitInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("poll", "spin_us", "poll_fallbacks", "poll_yields", "last_submit_us",
                                           "last_wait_us")]
+
+
+class CloudDesc(C.Structure):
+    """ag2_cloud_desc: a cloud with its camera split (size_left) and, optionally, the normals that came with it."""
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_size_t), ("stride_bytes", C.c_size_t), ("on_device", C.c_int),
+                ("size_left", C.c_size_t), ("normals", C.c_void_p), ("normals_stride_bytes", C.c_size_t)]
+
+
+def _rows_f32(a):
+    """(n, >= 3) float32 rows as they lie in memory when their elements are packed (any row stride), else a copy."""
+    a = np.asarray(a)
+    if a.dtype != np.float32 or a.ndim != 2 or (a.shape[0] and a.strides[1] != 4) or a.strides[0] % 4 or a.strides[0] < 12:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    assert a.ndim == 2 and a.shape[1] >= 3
+    return a
+
+
+def cloud_desc(xyz=None, size_left=None, normals=None, dptr=None, n=None, stride=12, normals_dptr=None,
+               normals_stride=12):
+    """(CloudDesc, arrays to keep alive).  Host memory: xyz (n, >= 3) float32 rows and normals (n, 3) float32 rows,
+    at whatever row stride they have (views into one record array give the interleaved form).  Device memory: dptr /
+    n / stride and normals_dptr / normals_stride.  size_left None = n (one camera)."""
+    d = CloudDesc()
+    keep = []
+    if dptr is None:
+        xyz = _rows_f32(xyz)
+        keep.append(xyz)
+        n = xyz.shape[0]
+        d.xyz, d.stride_bytes, d.on_device = xyz.ctypes.data, (xyz.strides[0] if n else 12), 0
+        if normals is not None:
+            normals = _rows_f32(normals)
+            assert normals.shape[0] == n
+            keep.append(normals)
+            d.normals, d.normals_stride_bytes = normals.ctypes.data, (normals.strides[0] if n else 12)
+    else:
+        d.xyz, d.stride_bytes, d.on_device = dptr, stride, 1
+        if normals_dptr is not None:
+            d.normals, d.normals_stride_bytes = normals_dptr, normals_stride
+    d.n = int(n)
+    d.size_left = int(n) if size_left is None else int(size_left)
+    return d, keep
 
 
 IS_SUM, IS_MAX = 1, 2
@@ -238,6 +280,13 @@ class Detector:
         self.n = n
         self._ck(self.L.ag2_set_cloud_device(self.h, C.c_void_p(dptr), C.c_size_t(n),
                                              C.c_size_t(stride_bytes)))
+
+    def set_cloud_desc(self, xyz=None, size_left=None, normals=None, **kw):
+        """ag2_set_cloud_desc: CloudCamera(cloud, size_left) / CloudCamera(cloud_normals, size_left) with camera mask
+        and normals packed on the device.  Arguments: cloud_desc()."""
+        d, keep = cloud_desc(xyz, size_left, normals, **kw)
+        self.n = int(d.n)
+        self._ck(self.L.ag2_set_cloud_desc(self.h, C.byref(d)))
 
     def preprocess_cloud(self, xyz, cam_source=None, normals=None, filter_workspace=True,
                          voxelize=True, voxel_size=0.003, flags=0):
@@ -480,6 +529,44 @@ class Detector:
                                          C.byref(ns), C.byref(na)))
         return sel[: ns.value].copy(), na.value
 
+    def _frame_buf(self, n_samples):
+        cap = max(1, n_samples * int(self.params.num_orientations))
+        nsel = int(self.params.num_selected)   # (a buffer of the selection's size, kept between calls: as in detect)
+        cap = cap if nsel < 0 else max(1, min(cap, nsel))
+        if getattr(self, "_sel_buf", None) is None or len(self._sel_buf) < cap:
+            self._sel_buf = np.zeros(cap, dtype=HYP_DTYPE)
+        return self._sel_buf, cap
+
+    def detect_frame_desc(self, xyz=None, sample_idx=None, seed=0, do_prune=True, size_left=None, normals=None, **kw):
+        """One frame of a stream of two-camera clouds and / or clouds with normals (ag2_detect_frame_desc).
+        Cloud arguments: cloud_desc().  Returns (selected records, n_scored)."""
+        si = np.ascontiguousarray(sample_idx, dtype=np.int32)
+        d, keep = cloud_desc(xyz, size_left, normals, **kw)
+        self.n = int(d.n)
+        sel, cap = self._frame_buf(len(si))
+        ns, na = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.L.ag2_detect_frame_desc(self.h, C.byref(d), _ptr(si), C.c_size_t(len(si)), C.c_uint64(seed),
+                                              C.c_int(1 if do_prune else 0), _ptr(sel), C.c_size_t(cap),
+                                              C.byref(ns), C.byref(na)))
+        return sel[: ns.value].copy(), na.value
+
+    def submit_frame_desc(self, xyz=None, sample_idx=None, seed=0, do_prune=True, size_left=None, normals=None, **kw):
+        """ag2_submit_frame_desc: detect_frame_desc up to the wait; wait_frame() brings the results.  A device-resident
+        cloud and its normals stay valid until then."""
+        si = np.ascontiguousarray(sample_idx, dtype=np.int32)
+        d, keep = cloud_desc(xyz, size_left, normals, **kw)
+        self.n = int(d.n)
+        self._pending_samples = len(si)
+        self._ck(self.L.ag2_submit_frame_desc(self.h, C.byref(d), _ptr(si), C.c_size_t(len(si)), C.c_uint64(seed),
+                                              C.c_int(1 if do_prune else 0)))
+
+    def wait_frame(self):
+        """ag2_wait_frame: (selected records, n_scored) of the frame submitted last."""
+        sel, cap = self._frame_buf(getattr(self, "_pending_samples", 0))
+        ns, na, nv = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.L.ag2_wait_frame(self.h, _ptr(sel), C.c_size_t(cap), C.byref(ns), C.byref(na), C.byref(nv)))
+        return sel[: ns.value].copy(), na.value
+
     def detect_frame_raw(self, xyz=None, num_samples=0, sample_seed=0, seed=0, do_prune=True, dptr=None, n=None,
                          stride=12, filter_workspace=True, voxel_size=0.003):
         """One frame of the RAW cloud (ag2_detect_frame_raw): workspace filter, voxel grid and uniform
@@ -666,6 +753,15 @@ class Pipe:
         cap = max(1, len(si) * int(self.params.num_orientations))
         self._ck(self.L.ag2_pipe_submit(self.h, ptr, C.c_int(on_dev), C.c_size_t(n), C.c_size_t(stride), _ptr(si),
                                         C.c_size_t(len(si)), C.c_uint64(seed), C.c_int(1 if do_prune else 0)))
+        self._caps.append(cap)
+
+    def submit_desc(self, xyz=None, sample_idx=None, seed=0, do_prune=True, size_left=None, normals=None, **kw):
+        """ag2_pipe_submit_desc; cloud arguments: cloud_desc().  (A host cloud is copied into staging inside the call.)"""
+        si = np.ascontiguousarray(sample_idx, dtype=np.int32)
+        d, keep = cloud_desc(xyz, size_left, normals, **kw)
+        cap = max(1, len(si) * int(self.params.num_orientations))
+        self._ck(self.L.ag2_pipe_submit_desc(self.h, C.byref(d), _ptr(si), C.c_size_t(len(si)), C.c_uint64(seed),
+                                             C.c_int(1 if do_prune else 0)))
         self._caps.append(cap)
 
     def wait(self):

@@ -33,6 +33,8 @@ struct FrameArgs {
   unsigned long long slot_base;
   unsigned long long sample_seed;  // ag2_detect_frame_raw: seed of the uniform sub-sampling
   unsigned long long seq;          // the frame's sequence number: k_topk writes it behind the results (FrameOut::done_seq)
+  // ag2_detect_frame_desc with normals: where k_gather_normals reads them (device address, stride in bytes, points)
+  unsigned long long nrm_src, nrm_stride, nrm_n;
 };
 
 // Per-context constants, built on the host (ag2_context.hip derive_constants) and read through a

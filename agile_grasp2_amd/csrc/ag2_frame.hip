@@ -32,6 +32,12 @@
 // cloud_camera.cpp:89-178) run on the device inside the same captured sequence (k_preprocess.hip:
 // enqueue_front_frame) -- the processed cloud, the search grid's description and the sample indices never
 // leave HBM, and there is still exactly one host synchronisation per frame.
+//
+// ag2_*_frame_desc take the clouds of the reference's robot launch file (launch/robot_detect_grasps.launch:4-6): two
+// cameras split at size_left (CloudCamera(cloud, size_left_cloud), cloud_camera.cpp:34-51) -- the camera bits are
+// written by the pack in front of the sequence -- and normals that came with the cloud (cloud_camera.cpp:4-31),
+// which k_gather_normals puts into sorted order where k_normals would compute them; its source, stride and point
+// count travel in FrameArgs.  Whether the frames bring normals is part of what a captured graph is valid for.
 #include <math.h>
 #include <string.h>
 
@@ -61,6 +67,7 @@ struct ag2_frame_state {
   size_t h_pin_bytes = 0;
   size_t off_idx = 0, off_out = 0, off_rec = 0;
   ag2::DevBuf d_raw;         // staging of a cloud handed over in host memory
+  ag2::DevBuf d_raw_nrm;     // ... and of its normals, when they are not part of the cloud's records
   int cap_p = 0;             // in-box points per image the captured renderers can take
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -70,6 +77,8 @@ struct ag2_frame_state {
   // ag2_detect_frame_raw: the shapes of the front end (raw == false: frames arrive preprocessed)
   bool raw = false;
   ag2::FrontShapes fs{};
+  // ag2_detect_frame_desc: the frames of the stream bring their normals (k_gather_normals in place of k_normals)
+  bool given_nrm = false;
   // a frame that has been submitted and not yet waited for (ag2_submit_frame* / ag2_wait_frame)
   struct Pending {
     bool active = false;
@@ -80,6 +89,10 @@ struct ag2_frame_state {
     const void* xyz = nullptr;   // the caller's buffer (device clouds) or the device staging copy
     int on_device = 0;
     size_t n = 0, stride = 12;
+    bool desc = false;           // ag2_*_frame_desc: size_left and normals below count
+    size_t size_left = 0;
+    const void* normals = nullptr;  // device memory: the caller's buffer, or the staging copy
+    size_t nrm_stride = 12;
     bool raw = false;
     int filter_ws = 1;
     double voxel_size = 0.003;
@@ -93,7 +106,10 @@ struct ag2_frame_state {
   unsigned seq = 0;              // sequence number of the last frame enqueued at fixed shapes (FrameArgs::seq)
   char* h_stage = nullptr;       // page-locked staging of a cloud handed over in host memory (true async H2D)
   size_t h_stage_bytes = 0;
+  char* h_stage_nrm = nullptr;   // ... and of normals handed over apart from the cloud's records
+  size_t h_stage_nrm_bytes = 0;
 };
+static_assert(sizeof(ag2::FrameArgs) <= 64, "the sample indices follow the per-frame scalars at offset 64 of the page-locked block");
 
 namespace ag2 {
 
@@ -285,7 +301,8 @@ unsigned long long frame_signature(const ag2_ctx* c, const ag2_frame_state* f) {
                                      (unsigned long long)c->min_inliers,
                                      (unsigned long long)c->origin_set, (unsigned long long)f->raw, f->fs.raw_max,
                                      f->fs.cap_words, f->fs.cand_cap, (unsigned long long)cell_bits,
-                                     (unsigned long long)f->fs.filter_workspace};
+                                     (unsigned long long)f->fs.filter_workspace,
+                                     (unsigned long long)f->given_nrm, (unsigned long long)c->p.n_cams};
   unsigned long long h = 1469598103934665603ull;
   auto mix = [&h](unsigned long long v) {
     for (int b = 0; b < 8; b++) {
@@ -344,7 +361,8 @@ int enqueue_frame(ag2_ctx* c, ag2_frame_state* f, int do_prune) {
   int rc = launch_grid_frame(c, cell, cell + cell_words);
   if (rc) return rc;
   // -- K1 normals ----------------------------------------------------------------------------------
-  rc = launch_normals(c);
+  // (normals that came with the frames are gathered into sorted order instead: source and stride in FrameArgs)
+  rc = f->given_nrm ? launch_gather_normals(c, nullptr, 0) : launch_normals(c);
   if (rc) return rc;
   // -- samples (indices in the page-locked block, padded with -1), K2 frames, K3 sweep -------------
   AG2_HIP(c, c->d_sample_q.reserve(s_max * 16));
@@ -391,6 +409,10 @@ struct FrameIn {
   const void* xyz = nullptr;
   int on_device = 0;
   size_t n = 0, stride = 12;
+  bool desc = false;  // ag2_*_frame_desc: the three below count (otherwise one camera, no normals)
+  size_t size_left = 0;
+  const void* normals = nullptr;
+  size_t nrm_stride = 12;
   bool raw = false;  // ag2_detect_frame_raw
   int filter_ws = 1;
   double voxel_size = 0.003;
@@ -401,6 +423,49 @@ struct FrameIn {
   uint64_t seed = 0;
   int do_prune = 1;
 };
+
+// a host buffer -> page-locked staging (the host copies) -> device staging (a true asynchronous DMA: the call does
+// not wait for the transfer)
+int stage_host(ag2_ctx* c, char** h, size_t* h_bytes, ag2::DevBuf& d, const void* src, size_t bytes) {
+  if (bytes > *h_bytes) {
+    AG2_HIP(c, ag2::stream_sync(c));
+    if (*h) (void)hipHostFree(*h);
+    *h = nullptr;
+    *h_bytes = 0;
+    const size_t want = bytes + bytes / 8 + 4096;
+    AG2_HIP(c, hipHostMalloc((void**)h, want, hipHostMallocDefault));
+    *h_bytes = want;
+  }
+  AG2_HIP(c, d.reserve(bytes));
+  memcpy(*h, src, bytes);
+  AG2_HIP(c, hipMemcpyAsync(d.p, *h, bytes, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// ag2_set_cloud_desc behind the staging: cloud and normals in device memory
+int set_cloud_desc_device(ag2_ctx* c, const void* d_xyz, size_t n, size_t stride, size_t size_left, const void* d_nrm,
+                          size_t nrm_stride) {
+  {  // (as ag2_set_cloud)
+    const int rcc = rank_spec_collect(c, /*stream_is_idle=*/false);
+    if (rcc) return rcc;
+  }
+  c->n = n;
+  c->has_cloud = c->has_normals = false;
+  c->bounds_known = false;
+  AG2_HIP(c, c->d_xyz_in.reserve(std::max<size_t>(n, 1) * 16));
+  int rc = pack_device_xyz(c, d_xyz, n, stride, c->d_xyz_in.as<float4>(), /*with_bounds=*/true, 0,
+                           c->p.n_cams == 2 ? (long long)size_left : -1ll);
+  if (rc) return rc;
+  rc = after_cloud(c);
+  if (rc) return rc;
+  if (d_nrm && c->n_valid) {
+    rc = launch_gather_normals(c, d_nrm, nrm_stride);
+    if (rc) return rc;
+    AG2_HIP(c, ag2::stream_sync(c));  // (the caller's buffers are free again on return, as after ag2_set_cloud)
+    c->has_normals = true;
+  }
+  return 0;
+}
 
 // the step-by-step path for one frame (also what sizes the buffers and teaches the shapes)
 int frame_stepwise(ag2_ctx* c, const void* d_xyz, const FrameIn& in, ag2_hypothesis* selected, size_t cap,
@@ -415,11 +480,13 @@ int frame_stepwise(ag2_ctx* c, const void* d_xyz, const FrameIn& in, ag2_hypothe
     if (!rc) rc = ag2_subsample_uniformly(c, in.num_samples, in.sample_seed, nullptr, 0, &k);  // indices stay on the device
     if (n_voxels) *n_voxels = m;
     s = k;
+  } else if (in.desc) {
+    rc = set_cloud_desc_device(c, d_xyz, in.n, in.stride, in.size_left, in.normals, in.nrm_stride);
   } else {
     rc = ag2_set_cloud_device(c, d_xyz, in.n, in.stride);
   }
   if (s_used) *s_used = s;
-  if (!rc) rc = ag2_compute_normals(c);
+  if (!rc && !(in.desc && in.normals)) rc = ag2_compute_normals(c);  // (given normals are used as they are)
   if (!rc)
     rc = ag2_detect(c, in.raw ? nullptr : in.sample_idx, nullptr, s, 0, in.seed, in.do_prune, selected, cap, n_selected,
                     nullptr, 0, n_scored);
@@ -445,6 +512,7 @@ void learn_shapes(ag2_ctx* c, ag2_frame_state* f, const FrameIn& in, size_t n_vo
     f->fs = FrontShapes{};
   }
   f->raw = in.raw;
+  f->given_nrm = in.normals != nullptr;
   const size_t n_cloud = in.raw ? n_vox : n;
   c->fm_n_max = std::max(c->fm_n_max, n_cloud + n_cloud / 8 + 1024);
   c->fm_s_max = in.raw ? s_used : std::max(c->fm_s_max, s_used);
@@ -494,6 +562,10 @@ FrameIn pending_in(const ag2_frame_state::Pending& p) {
   in.on_device = p.on_device;
   in.n = p.n;
   in.stride = p.stride;
+  in.desc = p.desc;
+  in.size_left = p.size_left;
+  in.normals = p.normals;
+  in.nrm_stride = p.nrm_stride;
   in.raw = p.raw;
   in.filter_ws = p.filter_ws;
   in.voxel_size = p.voxel_size;
@@ -529,7 +601,8 @@ int run_pending_stepwise(ag2_ctx* c, ag2_frame_state* f) {
 
 // ---- submit: everything of a frame up to (not including) the wait for its results -------------------
 int frame_submit_impl(ag2_ctx* c, const FrameIn& in) {
-  if (c->p.n_cams != 1) return set_err(c, AG2_ERR_ARG, "frames are single-camera clouds");
+  // (the signature of the older entries cannot say size_left: two-camera clouds come through ag2_*_frame_desc)
+  if (c->p.n_cams != 1 && !in.desc) return set_err(c, AG2_ERR_ARG, "frames are single-camera clouds");
   if (in.stride < 12 || in.stride % 4 != 0) return set_err(c, AG2_ERR_ARG, "bad stride");
   if (in.n > (size_t)1 << 30) return set_err(c, AG2_ERR_CAPACITY, "more than 2^30 points");
   if (in.raw && !((float)in.voxel_size > 0.f)) return set_err(c, AG2_ERR_ARG, "voxel_size must be positive");
@@ -548,27 +621,26 @@ int frame_submit_impl(ag2_ctx* c, const FrameIn& in) {
   // A cloud in host memory goes through page-locked staging (the host copies, then a true asynchronous
   // DMA: the call does not wait for the transfer) into a device staging buffer.
   const void* d_xyz = in.xyz;
+  const void* d_nrm = in.normals;
   if (!in.on_device && n) {
-    const size_t bytes = n * in.stride;
-    if (bytes > f->h_stage_bytes) {
-      AG2_HIP(c, ag2::stream_sync(c));
-      if (f->h_stage) (void)hipHostFree(f->h_stage);
-      f->h_stage = nullptr;
-      f->h_stage_bytes = 0;
-      const size_t want = bytes + bytes / 8 + 4096;
-      AG2_HIP(c, hipHostMalloc((void**)&f->h_stage, want, hipHostMallocDefault));
-      f->h_stage_bytes = want;
-    }
-    AG2_HIP(c, f->d_raw.reserve(bytes));
-    memcpy(f->h_stage, in.xyz, bytes);
-    AG2_HIP(c, hipMemcpyAsync(f->d_raw.p, f->h_stage, bytes, hipMemcpyHostToDevice, c->stream));
-    d_xyz = f->d_raw.p;
+    ag2_cloud_desc d{};
+    d.xyz = in.xyz;
+    d.n = n;
+    d.stride_bytes = in.stride;
+    d.normals = in.normals;
+    d.normals_stride_bytes = in.nrm_stride;
+    const int rcs = stage_cloud_desc(c, d, &d_xyz, &d_nrm);
+    if (rcs) return rcs;
   }
   p.active = true;
   p.xyz = d_xyz;
   p.on_device = 1;
   p.n = n;
   p.stride = in.stride;
+  p.desc = in.desc;
+  p.size_left = in.size_left;
+  p.normals = n ? d_nrm : nullptr;
+  p.nrm_stride = in.nrm_stride;
   p.raw = in.raw;
   p.filter_ws = in.filter_ws;
   p.voxel_size = in.voxel_size;
@@ -581,7 +653,8 @@ int frame_submit_impl(ag2_ctx* c, const FrameIn& in) {
   const size_t s_req = in.raw ? in.num_samples : in.s;
   // Frames the captured sequence cannot take: more than 65536 table slots, an empty frame.
   p.unsupported = s_req * (size_t)R > 65536 || n == 0 || s_req == 0;
-  if (f->shapes_known && f->raw != in.raw) {  // the stream changed its entry point: learn the shapes again
+  // the stream changed its entry point, or its frames started / stopped bringing normals: learn the shapes again
+  if (f->shapes_known && (f->raw != in.raw || f->given_nrm != (p.normals != nullptr))) {
     f->shapes_known = false;
     drop_graph(f);
   }
@@ -615,6 +688,9 @@ int frame_submit_impl(ag2_ctx* c, const FrameIn& in) {
   fa->sample_seed = in.sample_seed;
   if (++f->seq == 0u) f->seq = 1u;  // (zero is what the flag starts from)
   fa->seq = f->seq;
+  fa->nrm_src = (unsigned long long)(uintptr_t)p.normals;
+  fa->nrm_stride = in.nrm_stride;
+  fa->nrm_n = n;
   if (!in.raw) {
     int32_t* hidx = (int32_t*)(f->h_pin + f->off_idx);
     memcpy(hidx, in.sample_idx, in.s * 4);
@@ -624,7 +700,9 @@ int frame_submit_impl(ag2_ctx* c, const FrameIn& in) {
       c->d_griddesc.reserve(sizeof(GridDesc)) != hipSuccess)
     return fail(set_err(c, AG2_ERR_HIP, "frame: device allocation failed"));
   if (in.raw) rc = front_pack_raw(c, d_xyz, n, in.stride, f->fs);
-  else rc = pack_device_xyz(c, d_xyz, n, in.stride, c->d_xyz_in.as<float4>(), /*with_bounds=*/true, c->fm_n_max);
+  else
+    rc = pack_device_xyz(c, d_xyz, n, in.stride, c->d_xyz_in.as<float4>(), /*with_bounds=*/true, c->fm_n_max,
+                         c->p.n_cams == 2 ? (long long)in.size_left : -1ll);
   if (rc) return fail(rc);
   p.replay = f->use_graph && f->graph_valid && f->do_prune == in.do_prune && f->sig_at_capture == frame_signature(c, f);
   if (p.replay) {
@@ -806,9 +884,50 @@ void frame_release(ag2_ctx* c) {
   drop_graph(f);
   if (f->h_pin) (void)hipHostFree(f->h_pin);
   if (f->h_stage) (void)hipHostFree(f->h_stage);
+  if (f->h_stage_nrm) (void)hipHostFree(f->h_stage_nrm);
   f->d_raw.release();
+  f->d_raw_nrm.release();
   delete f;
   c->fm = nullptr;
+}
+
+int check_cloud_desc(ag2_ctx* c, const ag2_cloud_desc* d) {
+  if (!d) return set_err(c, AG2_ERR_ARG, "the cloud description is NULL");
+  if (d->n > 0 && !d->xyz) return set_err(c, AG2_ERR_ARG, "xyz is NULL");
+  if (d->stride_bytes < 12 || d->stride_bytes % 4 != 0) return set_err(c, AG2_ERR_ARG, "bad stride");
+  if (d->size_left > d->n) return set_err(c, AG2_ERR_ARG, "size_left is larger than n");
+  if (c->p.n_cams == 1 && d->size_left != d->n)
+    return set_err(c, AG2_ERR_ARG, "size_left must equal n on a one-camera context");
+  if (d->normals && (d->normals_stride_bytes < 12 || d->normals_stride_bytes % 4 != 0))
+    return set_err(c, AG2_ERR_ARG, "bad normals stride");
+  if (d->n > (size_t)1 << 30) return set_err(c, AG2_ERR_CAPACITY, "more than 2^30 points");
+  return 0;
+}
+
+// Normals that lie inside the cloud's records (PointXYZRGBNormal: xyz + 16) travel with them in ONE transfer; normals
+// of their own get a second staging pair.  (n records of 3 floats: the last one ends 12 bytes behind its start.)
+int stage_cloud_desc(ag2_ctx* c, const ag2_cloud_desc& d, const void** d_xyz, const void** d_nrm) {
+  *d_xyz = d.xyz;
+  *d_nrm = d.normals;
+  if (d.on_device || d.n == 0) return 0;
+  if (!c->fm) c->fm = new ag2_frame_state();
+  ag2_frame_state* f = c->fm;
+  const size_t bytes = d.n * d.stride_bytes;
+  int rc = stage_host(c, &f->h_stage, &f->h_stage_bytes, f->d_raw, d.xyz, bytes);
+  if (rc) return rc;
+  *d_xyz = f->d_raw.p;
+  if (d.normals) {
+    const size_t nbytes = (d.n - 1) * d.normals_stride_bytes + 12;
+    const char *x0 = (const char*)d.xyz, *n0 = (const char*)d.normals;
+    if (n0 >= x0 && n0 + nbytes <= x0 + bytes) {
+      *d_nrm = (const char*)f->d_raw.p + (n0 - x0);
+    } else {
+      rc = stage_host(c, &f->h_stage_nrm, &f->h_stage_nrm_bytes, f->d_raw_nrm, d.normals, nbytes);
+      if (rc) return rc;
+      *d_nrm = f->d_raw_nrm.p;
+    }
+  }
+  return 0;
 }
 
 }  // namespace ag2
@@ -830,6 +949,7 @@ int ag2_stream_configure(ag2_ctx* c, size_t max_points, size_t max_samples, int 
   f->cap_img = f->k_cap = 0;
   f->cap_p = 0;
   f->raw = false;
+  f->given_nrm = false;
   f->fs = FrontShapes{};
   memset(&f->info, 0, sizeof(f->info));
   return 0;
@@ -850,6 +970,60 @@ int ag2_detect_frame(ag2_ctx* c, const void* xyz, int xyz_on_device, size_t n, s
   in.seed = seed;
   in.do_prune = do_prune;
   return detect_frame_impl(c, in, selected, cap, n_selected, n_scored, nullptr);
+}
+
+// ---- the cloud given as a description: two cameras (size_left), normals that came with the cloud ----
+static int frame_in_from_desc(ag2_ctx* c, const ag2_cloud_desc* d, const int32_t* sample_idx, size_t s, uint64_t seed,
+                              int do_prune, FrameIn* in) {
+  const int rc = check_cloud_desc(c, d);
+  if (rc) return rc;
+  in->xyz = d->xyz;
+  in->on_device = d->on_device;
+  in->n = d->n;
+  in->stride = d->stride_bytes;
+  in->desc = true;
+  in->size_left = d->size_left;
+  in->normals = d->n ? d->normals : nullptr;
+  in->nrm_stride = d->normals ? d->normals_stride_bytes : 12;
+  in->sample_idx = sample_idx;
+  in->s = s;
+  in->seed = seed;
+  in->do_prune = do_prune;
+  return 0;
+}
+
+int ag2_set_cloud_desc(ag2_ctx* c, const ag2_cloud_desc* d) {
+  if (!c) return AG2_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  const int rc = check_cloud_desc(c, d);
+  if (rc) return rc;
+  if (c->fm && c->fm->pend.active)  // (the staging belongs to the frame in flight)
+    return set_err(c, AG2_ERR_STATE, "a frame is in flight on this context: ag2_wait_frame first");
+  const void *d_xyz = nullptr, *d_nrm = nullptr;
+  const int rcs = stage_cloud_desc(c, *d, &d_xyz, &d_nrm);
+  if (rcs) return rcs;
+  return set_cloud_desc_device(c, d_xyz, d->n, d->stride_bytes, d->size_left, d->n ? d_nrm : nullptr,
+                               d->normals ? d->normals_stride_bytes : 12);
+}
+
+int ag2_detect_frame_desc(ag2_ctx* c, const ag2_cloud_desc* d, const int32_t* sample_idx, size_t s, uint64_t seed,
+                          int do_prune, ag2_hypothesis* selected, size_t cap, size_t* n_selected, size_t* n_scored) {
+  if (!c || !n_selected || (s && !sample_idx)) return AG2_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  FrameIn in;
+  const int rc = frame_in_from_desc(c, d, sample_idx, s, seed, do_prune, &in);
+  if (rc) return rc;
+  return detect_frame_impl(c, in, selected, cap, n_selected, n_scored, nullptr);
+}
+
+int ag2_submit_frame_desc(ag2_ctx* c, const ag2_cloud_desc* d, const int32_t* sample_idx, size_t s, uint64_t seed,
+                          int do_prune) {
+  if (!c || (s && !sample_idx)) return AG2_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  FrameIn in;
+  const int rc = frame_in_from_desc(c, d, sample_idx, s, seed, do_prune, &in);
+  if (rc) return rc;
+  return frame_submit(c, in);
 }
 
 int ag2_detect_frame_raw(ag2_ctx* c, const void* xyz, int xyz_on_device, size_t n, size_t stride_bytes,
@@ -997,6 +1171,17 @@ int ag2_pipe_submit(ag2_pipe* q, const void* xyz, int xyz_on_device, size_t n, s
   }
   ag2_ctx* c = q->ctx[q->next_submit];
   return pipe_submitted(q, c, ag2_submit_frame(c, xyz, xyz_on_device, n, stride_bytes, sample_idx, s, seed, do_prune));
+}
+
+int ag2_pipe_submit_desc(ag2_pipe* q, const ag2_cloud_desc* d, const int32_t* sample_idx, size_t s, uint64_t seed,
+                         int do_prune) {
+  if (!q) return AG2_ERR_ARG;
+  if (q->in_flight == q->ctx.size()) {
+    q->err = "pipe full: ag2_pipe_wait first";
+    return AG2_ERR_STATE;
+  }
+  ag2_ctx* c = q->ctx[q->next_submit];
+  return pipe_submitted(q, c, ag2_submit_frame_desc(c, d, sample_idx, s, seed, do_prune));
 }
 
 int ag2_pipe_wait(ag2_pipe* q, ag2_hypothesis* selected, size_t cap, size_t* n_selected, size_t* n_scored,

@@ -408,7 +408,15 @@ inline hipError_t stage_sync(ag2_ctx* c, int i) {
 }
 int gather_normals(ag2_ctx* c);  // d_tmp (float4, original order) -> d_nrm (sorted order)
 int pack_device_xyz(ag2_ctx* c, const void* d_xyz, size_t n, size_t stride_bytes, float4* dst,
-                    bool with_bounds = false, size_t n_pad = 0);
+                    bool with_bounds = false, size_t n_pad = 0, long long size_left = -1);
+// normals given with the cloud (3 floats at a stride, original order, device memory) -> d_nrm (sorted order); frame
+// mode: at the fixed maximum, source and stride from FrameArgs
+int launch_gather_normals(ag2_ctx* c, const void* d_nrm_src, size_t stride_bytes);
+// ag2_frame.hip: a cloud (and its normals) in host memory -> page-locked staging -> device staging, asynchronous;
+// *d_xyz / *d_nrm: where the kernels read them (the caller's own pointers for a device-resident cloud)
+int stage_cloud_desc(ag2_ctx* c, const ag2_cloud_desc& d, const void** d_xyz, const void** d_nrm);
+// argument checks the description entries share
+int check_cloud_desc(ag2_ctx* c, const ag2_cloud_desc* d);
 // frame mode: grid description derived on the device + cell count + scan + scatter + cell sort at the
 // fixed maxima
 int launch_grid_frame(ag2_ctx* c, unsigned* cell, unsigned* zeroed_ctl);

@@ -34,9 +34,12 @@ __global__ void k_pack_xyz(const char* __restrict__ src, size_t stride, int n,
 static_assert(kBoundsBlocks * 32 <= (int)kPinDoneFlag, "extent partials must fit the small read-back area in front of the flags");
 // n_pad > n (frame mode): xyz[n .. n_pad) is filled with non-finite points, which no later stage
 // ever sees as a point -- the launches of a captured frame run over the fixed maximum n_pad.
+// size_left (PACK): CloudCamera(cloud, size_left_cloud), cloud_camera.cpp:34-51 -- points [0, size_left) carry
+// camera bit 0, the rest bit 1 (the mask encoding of ag2_set_cloud); a one-camera cloud passes INT_MAX.  The pack
+// runs in front of a captured frame, never inside it: the value is not frozen into a graph.
 template <bool PACK>
 __global__ void __launch_bounds__(256) k_bounds(const char* __restrict__ src, size_t stride,
-                                                float4* __restrict__ xyz, int n, int n_pad,
+                                                float4* __restrict__ xyz, int n, int n_pad, int size_left,
                                                 int* __restrict__ part, DevStats* st,
                                                 int* __restrict__ part_dev, uint4* __restrict__ zero16, int n_zero16) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *st = DevStats{};
@@ -52,7 +55,7 @@ __global__ void __launch_bounds__(256) k_bounds(const char* __restrict__ src, si
     if (PACK) {
       if (i < n) {
         const float* q = (const float*)(src + (size_t)i * stride);
-        p = make_float4(q[0], q[1], q[2], __int_as_float(1));
+        p = make_float4(q[0], q[1], q[2], __int_as_float(i < size_left ? 1 : 2));
       } else {
         p = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), 0.f);
       }
@@ -391,6 +394,43 @@ __global__ void k_gather4(const float4* __restrict__ src, const int* __restrict_
   if (i < n) dst[i] = src[perm[i]];
 }
 
+// Normals that came with the cloud (3 floats at a stride, in the cloud's order: the normal_x/y/z fields of a
+// PointNormal / PointXYZRGBNormal record, cloud_camera.cpp:27-31) -> float4 (nx, ny, nz, 0) in sorted order, taken
+// as they are.  k_gather4 without the widened intermediate in original order.
+// Frame mode: the launch covers the frame's maximum point count and the threads beyond the valid count of the
+// device-side grid description leave, as in k_normals; source, stride and point count change with every frame and
+// are read from the page-locked FrameArgs, not from arguments frozen into the graph.
+// Loads: lane i reads record perm[i] -- neighbours in space, not in memory -- so the lanes of a wave have no
+// consecutive records to load as whole dwordx4 rows and hand round; every lane fetches its own 12 bytes.
+__global__ void __launch_bounds__(256) k_gather_normals(const char* __restrict__ src, size_t stride, int n, int n_valid,
+                                                        const GridDesc* __restrict__ gp,
+                                                        const FrameArgs* __restrict__ fa,
+                                                        const int* __restrict__ perm, float4* __restrict__ dst) {
+  if (fa) {
+    src = reinterpret_cast<const char*>((uintptr_t)fa->nrm_src);
+    stride = (size_t)fa->nrm_stride;
+    n = (int)fa->nrm_n;
+  }
+  if (gp) n_valid = gp->n_valid;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_valid) return;
+  const int j = perm[i];
+  if ((unsigned)j >= (unsigned)n) return;  // (perm holds indices of this cloud; never read beyond the caller's buffer)
+  const float* q = (const float*)(src + (size_t)j * stride);
+  dst[i] = make_float4(q[0], q[1], q[2], 0.f);
+}
+
+int launch_gather_normals(ag2_ctx* c, const void* d_nrm_src, size_t stride_bytes) {
+  if (!c->fm_on && c->n_valid == 0) return 0;
+  const int nb = ((int)(c->fm_on ? c->fm_n_max : c->n_valid) + 255) / 256;
+  hipLaunchKernelGGL(k_gather_normals, dim3(nb), dim3(256), 0, c->stream, (const char*)d_nrm_src, stride_bytes,
+                     (int)c->n, (int)c->n_valid, c->fm_on ? c->d_griddesc.as<GridDesc>() : (const GridDesc*)nullptr,
+                     c->fm_on ? c->fm_args_dev : (const FrameArgs*)nullptr, c->d_perm.as<int>(),
+                     c->d_nrm.as<float4>());
+  AG2_HIP(c, hipGetLastError());
+  return 0;
+}
+
 int gather_normals(ag2_ctx* c) {
   hipLaunchKernelGGL(k_gather4, dim3(((int)c->n_valid + 255) / 256), dim3(256), 0, c->stream,
                      c->d_tmp.as<float4>(), c->d_perm.as<int>(), (int)c->n_valid,
@@ -401,8 +441,9 @@ int gather_normals(ag2_ctx* c) {
 
 // with_bounds: the pack also produces the extent partials build_grid needs (c->bounds_blocks > 0
 // tells build_grid they are there), one pass over the source instead of two.
+// size_left < 0: a one-camera cloud (mask 1 for every point); otherwise the two-camera split (with_bounds only).
 int pack_device_xyz(ag2_ctx* c, const void* d_xyz, size_t n, size_t stride_bytes, float4* dst,
-                    bool with_bounds, size_t n_pad) {
+                    bool with_bounds, size_t n_pad, long long size_left) {
   c->bounds_blocks = 0;
   if (n == 0) return 0;
   if (n_pad < n) n_pad = n;  // (0 = no padding)
@@ -425,7 +466,9 @@ int pack_device_xyz(ag2_ctx* c, const void* d_xyz, size_t n, size_t stride_bytes
     const bool ahead = !c->fm_on && c->bounds_in_pin && c->cell_bytes_last && c->d_cell.p && n_pad == n;
     const size_t guess = ahead ? std::min(c->d_cell.bytes & ~size_t(15), (c->cell_bytes_last + c->cell_bytes_last / 4 + 15) & ~size_t(15)) : 0;
     hipLaunchKernelGGL(k_bounds<true>, dim3(nb), dim3(256), 0, c->stream, (const char*)d_xyz,
-                       stride_bytes, dst, (int)n, (int)n_pad, part, c->d_stats.as<DevStats>(),
+                       stride_bytes, dst, (int)n, (int)n_pad,
+                       size_left < 0 ? 0x7fffffff : (int)std::min<long long>(size_left, 0x7fffffff), part,
+                       c->d_stats.as<DevStats>(),
                        ahead ? c->d_bounds.as<int>() : (int*)nullptr,
                        ahead ? c->d_cell.as<uint4>() : (uint4*)nullptr, (int)(guess / 16));
     c->bounds_blocks = nb;
@@ -540,7 +583,7 @@ int build_grid(ag2_ctx* c) {
       nb = std::min((n + 255) / 256, kBoundsBlocks);
       AG2_HIP(c, c->d_bounds.reserve((size_t)kBoundsBlocks * 8 * 4));
       hipLaunchKernelGGL(k_bounds<false>, dim3(nb), dim3(256), 0, c->stream, (const char*)nullptr,
-                         (size_t)0, c->d_xyz_in.as<float4>(), n, n, c->d_bounds.as<int>(), st, (int*)nullptr,
+                         (size_t)0, c->d_xyz_in.as<float4>(), n, n, 0, c->d_bounds.as<int>(), st, (int*)nullptr,
                          (uint4*)nullptr, 0);
     }
     if (packed_blocks && c->bounds_in_pin) {  // the pack kernel wrote them into pin_small itself

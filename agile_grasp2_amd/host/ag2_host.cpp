@@ -1237,6 +1237,77 @@ std::vector<GraspHypothesis> GraspDetector::detectGraspPosesInFrame(const PointC
   return out;
 }
 
+bool GraspDetector::sizedFrameOnDevice(const ag2_cloud_desc& cloud, std::vector<GraspHypothesis>* out) {
+  const bool one_call = p_.antipodal_mode == PREDICTION && !use_incoming_samples_ && p_.devices.size() <= 1 &&
+                        cloud.size_left < cloud.n && classifier_ && classifier_->ok();
+  if (!one_call) return false;
+  std::shared_ptr<ag2::Context> ctx = contextFor(2);
+  if (!ctx) {
+    fprintf(stderr, "GraspDetector: %s\n", err_.c_str());
+    return true;
+  }
+  ag2_ctx* c = ctx->get();
+  int rc = classifier_->loadInto(*ctx);
+  const int hs_inliers = handle_search_.getMinInliers();
+  if (!rc) rc = ag2_set_min_inliers(c, hs_inliers > 0 ? hs_inliers : 0);
+  const std::vector<int32_t> idx(indices_.begin(), indices_.end());
+  const bool do_prune = indices_.empty();  // grasp_detector.cpp:149-160
+  std::vector<ag2_hypothesis> recs(std::max<size_t>(1, idx.size() * (size_t)p_.num_orientations));
+  size_t n = 0, n_scored = 0;
+  if (!rc)
+    rc = ag2_detect_frame_desc(c, &cloud, idx.data(), idx.size(), p_.seed, do_prune ? 1 : 0, recs.data(), recs.size(), &n,
+                               &n_scored);
+  resident_ctx_ = nullptr;  // (the context's cloud is this frame's, not a CloudCamera's)
+  if (rc) {
+    err_ = ag2_last_error(c);
+    fprintf(stderr, "GraspDetector::detectGraspPosesInFrame: %s\n", err_.c_str());
+    return true;
+  }
+  (void)ag2_get_stage_times(c, &times_);
+  (void)ag2_get_counters(c, &counters_);
+  out->reserve(n);
+  for (size_t h = 0; h < n; h++) out->push_back(GraspHypothesis(recs[h]));
+  return true;
+}
+
+std::vector<GraspHypothesis> GraspDetector::detectGraspPosesInFrame(const PointCloudRGB::Ptr& cloud, int size_left_cloud) {
+  std::vector<GraspHypothesis> out;
+  if (!cloud || cloud->size() == 0) {  // grasp_detector.cpp:86-91
+    fprintf(stderr, "Point cloud is empty!\n");
+    return out;
+  }
+  if (indices_.empty()) return out;  // (the topic path without an index list has no samples)
+  ag2_cloud_desc d{};
+  d.xyz = &cloud->points[0].x;
+  d.n = cloud->size();
+  d.stride_bytes = sizeof(ag2::PointXYZRGBA);
+  d.size_left = (size_t)std::max(size_left_cloud, 0);
+  if (size_left_cloud >= 0 && sizedFrameOnDevice(d, &out)) return out;
+  CloudCamera cc(cloud, size_left_cloud);
+  cc.setSampleIndices(indices_);
+  return detectGraspPoses(cc);
+}
+
+std::vector<GraspHypothesis> GraspDetector::detectGraspPosesInFrame(const PointCloudNormal::Ptr& cloud, int size_left_cloud) {
+  std::vector<GraspHypothesis> out;
+  if (!cloud || cloud->size() == 0) {  // grasp_detector.cpp:86-91
+    fprintf(stderr, "Point cloud is empty!\n");
+    return out;
+  }
+  if (indices_.empty()) return out;
+  ag2_cloud_desc d{};
+  d.xyz = &cloud->points[0].x;
+  d.n = cloud->size();
+  d.stride_bytes = sizeof(ag2::PointXYZRGBNormal);
+  d.size_left = (size_t)std::max(size_left_cloud, 0);
+  d.normals = &cloud->points[0].normal_x;  // inside the records: one transfer brings both
+  d.normals_stride_bytes = sizeof(ag2::PointXYZRGBNormal);
+  if (size_left_cloud >= 0 && sizedFrameOnDevice(d, &out)) return out;
+  CloudCamera cc(cloud, size_left_cloud);
+  cc.setSampleIndices(indices_);
+  return detectGraspPoses(cc);
+}
+
 // ---- Params::devices: N GPUs from the one process of the node ---------------------------------------------------
 // Replicated cloud (TILING_REPLICATE): every device holds the whole cloud (a 300 k-point cloud is 4.8 MB) and takes
 // a contiguous range of the sample list.  Spatial tiles (TILING_SPATIAL, BASELINE configuration 4): the list --

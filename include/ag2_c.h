@@ -224,7 +224,8 @@ int ag2_detect(ag2_ctx* c, const int32_t* sample_idx, const double* sample_xyz, 
  * maximum shapes with no host round trip before the results and is captured in a hipGraph that later
  * frames replay; the first frame (and any frame that outgrows the shapes: more points, samples or
  * grid cells, a longer point-list arena) runs step by step and sets them.  xyz: n points stride_bytes
- * apart in device (xyz_on_device != 0) or host memory; single-camera clouds.
+ * apart in device (xyz_on_device != 0) or host memory; single-camera clouds (two cameras, given normals:
+ * ag2_detect_frame_desc below).
  * ag2_stream_configure is optional: it presets the maxima (0 = learn from the first frame) and can
  * turn the graph off (the fixed-shape sequence is then launched kernel by kernel). */
 int ag2_stream_configure(ag2_ctx* c, size_t max_points, size_t max_samples, int use_graph);
@@ -249,6 +250,48 @@ int ag2_detect_frame_raw(ag2_ctx* c, const void* xyz, int xyz_on_device, size_t 
                          uint64_t seed, int do_prune, ag2_hypothesis* selected, size_t cap,
                          size_t* n_selected, size_t* n_scored, size_t* n_voxels);
 int ag2_get_frame_info(ag2_ctx* c, ag2_frame_info* out);
+
+/* ---- sized clouds and sensor normals on the device and frame paths ----
+ * The clouds of the reference's robot launch file (launch/robot_detect_grasps.launch:4-6): a two-camera
+ * CloudSized message -- CloudCamera(cloud, size_left_cloud), cloud_camera.cpp:34-51: points [0, size_left) were
+ * seen by camera 0, the rest by camera 1 -- and clouds that arrive WITH normals (normal_x/y/z fields,
+ * grasp_detection_node.cpp:220-226,243-248,266-270; CloudCamera(cloud_normals, size_left_cloud),
+ * cloud_camera.cpp:4-31), for which the hand search skips calculateNormalsOMP (hand_search.cpp:20,25-29).
+ *   xyz           n records, stride_bytes apart (a multiple of 4, at least 12), 3 floats at offset 0
+ *   on_device     xyz (and normals) live in device memory; otherwise in host memory
+ *   size_left     must equal n on a one-camera context (ag2_params.n_cams == 1), <= n on a two-camera context
+ *   normals       NULL, or n records of 3 floats, normals_stride_bytes apart (a multiple of 4, at least 12).  May
+ *                 point into the xyz records (the 48-byte PointXYZRGBNormal: xyz + 16, both strides 48).  Used as
+ *                 they are, NaN included. */
+typedef struct ag2_cloud_desc {
+  const void* xyz;
+  size_t n, stride_bytes;
+  int on_device;
+  size_t size_left;
+  const void* normals;
+  size_t normals_stride_bytes;
+} ag2_cloud_desc;
+/* The context state ag2_set_cloud(xyz, n, stride, cam_source, n_cams, normals) leaves for the camera matrix of
+ * cloud_camera.cpp:34-51 and the same normals widened to double, byte for byte -- with camera mask and normals
+ * packed ON THE DEVICE: bit 0 for i < size_left and bit 1 otherwise on a two-camera context, 1 on a one-camera
+ * context (as ag2_set_cloud_device).  A cloud in host memory goes through the page-locked staging of the frame
+ * path; there is no per-point host loop.  With normals the context needs no ag2_compute_normals (which would
+ * replace them by computed ones, as after ag2_set_cloud). */
+int ag2_set_cloud_desc(ag2_ctx* c, const ag2_cloud_desc* cloud);
+/* ag2_detect_frame / ag2_submit_frame / ag2_pipe_submit with the cloud given as a description: two-camera clouds
+ * and given normals inside the fixed-shape, captured sequence (the gather of the given normals takes the place of
+ * k_normals).  Same bytes as ag2_set_cloud_desc [+ ag2_compute_normals when normals == NULL] + ag2_detect with index
+ * samples and slot base 0, which is also the step-by-step form of such a frame.  size_left changes from frame to
+ * frame without a new capture; whether normals are given is part of what a captured graph is valid for: a stream that
+ * changes it learns its shapes again and captures again.  A one-camera cloud without normals takes exactly the path
+ * of ag2_detect_frame.  Results of ag2_submit_frame_desc through ag2_wait_frame; a device-resident cloud AND its
+ * normals stay valid until the wait.
+ * Not offered: RAW two-camera frames (ag2_detect_frame_raw stays single-camera).  The voxel grid's camera source
+ * follows the reference's literal scan-order indexing (cloud_camera.cpp:137-152), which needs the first hits in scan
+ * order; the front end of a raw frame does not compact and cannot give them.  ag2_preprocess_cloud handles two
+ * cameras. */
+int ag2_detect_frame_desc(ag2_ctx* c, const ag2_cloud_desc* cloud, const int32_t* sample_idx, size_t s, uint64_t seed,
+                          int do_prune, ag2_hypothesis* selected, size_t cap, size_t* n_selected, size_t* n_scored);
 
 /* How the host waits for results (no counterpart in the reference, which computes on the calling thread).
  * The last kernel of a step writes its results and then a sequence number into coherent page-locked memory;
@@ -283,6 +326,8 @@ int ag2_submit_frame(ag2_ctx* c, const void* xyz, int xyz_on_device, size_t n, s
 int ag2_submit_frame_raw(ag2_ctx* c, const void* xyz, int xyz_on_device, size_t n, size_t stride_bytes,
                          int filter_workspace, double voxel_size, size_t num_samples, uint64_t sample_seed,
                          uint64_t seed, int do_prune);
+int ag2_submit_frame_desc(ag2_ctx* c, const ag2_cloud_desc* cloud, const int32_t* sample_idx, size_t s, uint64_t seed,
+                          int do_prune);
 int ag2_wait_frame(ag2_ctx* c, ag2_hypothesis* selected, size_t cap, size_t* n_selected, size_t* n_scored,
                    size_t* n_voxels);
 /* ag2_pipe: `depth` contexts on one GPU (own streams), taken in turn by ONE caller thread -- while LeNet and the
@@ -299,6 +344,8 @@ int ag2_pipe_lenet_load(ag2_pipe* q, const float* conv1_w, const float* conv1_b,
                         const float* ip2_b);
 int ag2_pipe_submit(ag2_pipe* q, const void* xyz, int xyz_on_device, size_t n, size_t stride_bytes,
                     const int32_t* sample_idx, size_t s, uint64_t seed, int do_prune);
+int ag2_pipe_submit_desc(ag2_pipe* q, const ag2_cloud_desc* cloud, const int32_t* sample_idx, size_t s, uint64_t seed,
+                         int do_prune);
 int ag2_pipe_submit_raw(ag2_pipe* q, const void* xyz, int xyz_on_device, size_t n, size_t stride_bytes,
                         int filter_workspace, double voxel_size, size_t num_samples, uint64_t sample_seed,
                         uint64_t seed, int do_prune);

@@ -92,6 +92,17 @@ class GraspDetector {
   // front end: one camera, voxelize, no incoming samples or indices, antipodal_mode PREDICTION; any other
   // setting takes the two calls.
   std::vector<GraspHypothesis> detectGraspPosesInFrame(const PointCloudRGB::Ptr& raw_cloud);
+  // One frame of the robot launch file's stream (launch/robot_detect_grasps.launch:4-6): a two-camera CloudSized
+  // cloud (grasp_detection_node.cpp:239-259) -- or, second overload, one that brings its normals (:220-226,243-248;
+  // the hand search then skips calculateNormalsOMP, hand_search.cpp:20,25-29) -- taken as it arrives, without
+  // preprocessPointCloud, with the samples of the detector's index list (setIndicesFromMsg; the topic path :123-143
+  // and the find_grasps service :177-193).  The same hands as CloudCamera(cloud, size_left_cloud) + setSampleIndices
+  // + detectGraspPoses, in ONE GPU call (ag2_detect_frame_desc: camera mask and normals packed on the device, the
+  // per-frame pipeline in one captured sequence).  With indices set the prune is skipped (grasp_detector.cpp:150-160).
+  // No indices: nothing, as the topic path.  Outside antipodal_mode PREDICTION, with several devices, incoming
+  // samples, or size_left_cloud == size (the one-camera constructor's all-zero camera matrix): the three calls.
+  std::vector<GraspHypothesis> detectGraspPosesInFrame(const PointCloudRGB::Ptr& cloud, int size_left_cloud);
+  std::vector<GraspHypothesis> detectGraspPosesInFrame(const PointCloudNormal::Ptr& cloud, int size_left_cloud);
 
   static bool isScoreGreater(const GraspHypothesis& a, const GraspHypothesis& b) {
     return a.getScore() > b.getScore();
@@ -156,6 +167,8 @@ class GraspDetector {
                        int min_inliers, std::vector<ag2_hypothesis>* recs, size_t* n);
 
   bool preprocessOnDevice(CloudCamera& cloud_cam);
+  // the sized frame of either record type; false: the caller takes the three calls
+  bool sizedFrameOnDevice(const ag2_cloud_desc& cloud, std::vector<GraspHypothesis>* out);
 
   Params p_;
   int num_samples_;

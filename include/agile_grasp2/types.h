@@ -86,6 +86,7 @@ struct PointXYZRGBNormal {
   float curvature = 0;
   uint32_t pad2[2] = {0, 0};
 };
+static_assert(sizeof(PointXYZRGBNormal) == 48, "PointXYZRGBNormal must mirror PCL's 48-byte layout (normals at offset 16)");
 
 template <class P>
 struct PointCloud {
